@@ -122,7 +122,32 @@ def parse():
     ap.add_argument("--precision", default="fp16x3", choices=["fp16x3", "bf16x6", "fp32"],
                     help="3x3 conv arithmetic: fp32 emulated on the 16-bit matrix cores (fp16 hi/lo split, 3 products; "
                          "bf16 3-way split, 6 products) or exact-fp32 MFMA")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the samples of the last timed step to DIR/samples.npy (float32; a fixed "
+                         "seeded sample of at most 64 MB, with its flat indices in DIR/samples_index.npy, when larger)")
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return args
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(out, dirname):
+    """What the timed path hands its caller -- the samples of the last timed step -- as float32 .npy files.  The inputs are the
+    same from run to run (seeded weights and noise), so two builds can be compared file by file.  Above DUMP_LIMIT_BYTES a fixed
+    seeded set of elements is written instead, in increasing flat order, with those indices (float64, exact) next to it."""
+    import numpy as np
+    os.makedirs(dirname, exist_ok=True)
+    a = out.detach().float().cpu().contiguous().reshape(-1)
+    k = DUMP_LIMIT_BYTES // (4 + 8)
+    if a.numel() * 4 > DUMP_LIMIT_BYTES:
+        idx = torch.randperm(a.numel(), generator=torch.Generator().manual_seed(0))[:k].sort().values
+        np.save(os.path.join(dirname, "samples_index.npy"), idx.double().numpy())
+        np.save(os.path.join(dirname, "samples.npy"), a[idx].numpy())
+    else:
+        np.save(os.path.join(dirname, "samples.npy"), a.reshape(out.shape).numpy())
 
 
 def build_module(args, dev):
@@ -721,6 +746,8 @@ def main():
         dist.all_gather(allr, mine)
         per_rank = [[round(float(v), 3) for v in r.tolist()] for r in allr]
     assert out.shape[0] == B * world and bool(torch.isfinite(out).all())
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(out, args.dump_outputs)
     if rank == 0:
         value = B * world * args.steps / dt
         line = {

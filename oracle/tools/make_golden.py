@@ -12,7 +12,9 @@ import torch
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, HERE)
+sys.path.insert(0, os.path.dirname(os.path.dirname(HERE)))
 import refshim  # noqa: E402
+from tests.golden_util import cpu_vendor  # noqa: E402
 
 refshim.install()
 import diffsci.models as M  # noqa: E402
@@ -59,7 +61,7 @@ class RandnRecorder:
 # ---------------------------------------------------------------- 1. schedule tables
 def schedule():
     s = M.EDMScheduler()
-    arrs = {"cpu_capability": np.array(torch.backends.cpu.get_cpu_capability())}
+    arrs = {"cpu_capability": np.array(torch.backends.cpu.get_cpu_capability()), "cpu_vendor": np.array(cpu_vendor())}
     for n in (2, 5, 10, 18, 50, 100, 256):
         arrs[f"steps_{n}"] = s.create_steps(n + 1)
     tq = torch.tensor([80.0, 57.5, 10.0, 1.0, 0.3, 0.01, 0.002])

@@ -177,7 +177,7 @@ def test_receptive_field_matches_the_reference_formula():
     assert M.PUNetG(M.PUNetGConfig(model_channels=8)).calculate_receptive_field()["rf"] == float("inf")
 
 
-def test_lightning_checkpoint_loads_on_the_host():
+def test_lightning_checkpoint_loads_on_the_host(tmp_path):
     """karrasmodule.py:410-429: the reference's .ckpt layout (fixture written from a reference module by make_golden.py)."""
     import numpy as np
     import torch
@@ -193,5 +193,5 @@ def test_lightning_checkpoint_loads_on_the_host():
     sd = torch.load(path, map_location="cpu", weights_only=False)["state_dict"]
     assert all(torch.equal(module.state_dict()[k], sd[k]) for k in keys)
     with pytest.raises(KeyError):
-        torch.save({"weights": {}}, "/tmp/not_lightning.ckpt")
-        M.KarrasModule.load_from_checkpoint("/tmp/not_lightning.ckpt", model=net, config=cfg)
+        torch.save({"weights": {}}, tmp_path / "not_lightning.ckpt")
+        M.KarrasModule.load_from_checkpoint(str(tmp_path / "not_lightning.ckpt"), model=net, config=cfg)

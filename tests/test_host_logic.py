@@ -12,14 +12,13 @@ import diffsci_amd.models as M
 from diffsci_amd.models.karras.steptable import build_step_table
 from diffsci_amd.parallel import global_white_noise, shard_rows
 from oracle import karras_ref as K
-from tests.golden_util import load
+from tests.golden_util import load, same_cpu_arithmetic
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def _exact_on_same_isa(got, want):
-    v, _ = load("schedule")
-    if v["cpu_capability"] == torch.backends.cpu.get_cpu_capability():
+    if same_cpu_arithmetic():
         assert torch.equal(got, want)
     else:
         torch.testing.assert_close(got, want, rtol=3e-7, atol=0)
@@ -355,6 +354,30 @@ def test_bench_self_launch_relays_the_rank_zero_line_and_the_exit_code(tmp_path,
     assert rc != 0                                             # a failing rank fails the run
     cmd = bench.launcher_command(["--gpus", "4"], 4, 1234)
     assert cmd[1:3] == ["-m", "torch.distributed.run"] and "--nproc-per-node=4" in cmd and cmd[-3].endswith("bench.py")
+
+
+def test_bench_dump_outputs_whole_and_sampled(tmp_path, monkeypatch):
+    """bench.py --dump-outputs: the samples as float32 .npy; above the size limit a seeded element sample that is the same
+    from call to call, with its flat indices next to it."""
+    import importlib.util
+    import numpy as np
+    spec = importlib.util.spec_from_file_location("bench_for_dump", os.path.join(ROOT, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    x = torch.randn(4, 1, 8, 8, generator=torch.Generator().manual_seed(3))
+    bench.dump_outputs(x, str(tmp_path / "whole"))
+    got = np.load(tmp_path / "whole" / "samples.npy")
+    assert got.dtype == np.float32 and np.array_equal(got, x.numpy()) and not (tmp_path / "whole" / "samples_index.npy").exists()
+    bench.DUMP_LIMIT_BYTES = 800
+    for d in ("s1", "s2"):
+        bench.dump_outputs(x, str(tmp_path / d))
+    v, i = np.load(tmp_path / "s1" / "samples.npy"), np.load(tmp_path / "s1" / "samples_index.npy")
+    assert v.dtype == np.float32 and i.dtype == np.float64 and v.nbytes + i.nbytes <= 800 and (np.diff(i) > 0).all()
+    assert np.array_equal(v, x.numpy().reshape(-1)[i.astype(np.int64)])
+    assert np.array_equal(v, np.load(tmp_path / "s2" / "samples.npy")) and np.array_equal(i, np.load(tmp_path / "s2" / "samples_index.npy"))
+    monkeypatch.setattr(bench.sys, "argv", ["bench.py", "--steps", "0"])
+    with pytest.raises(SystemExit):                            # --steps is the number of timed steps: at least one
+        bench.parse()
 
 
 def test_global_noise_skip_ahead_is_self_checked(monkeypatch):

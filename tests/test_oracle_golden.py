@@ -8,7 +8,7 @@ import torch
 
 from oracle import karras_ref as K
 from oracle import mlp_ref, punetg_ref
-from tests.golden_util import load, rel_l2
+from tests.golden_util import load, rel_l2, same_cpu_arithmetic
 
 torch.set_num_threads(8)
 
@@ -16,8 +16,7 @@ SAME_ISA = None
 
 
 def _same_isa():
-    v, _ = load("schedule")
-    return v["cpu_capability"] == torch.backends.cpu.get_cpu_capability()
+    return same_cpu_arithmetic()
 
 
 def assert_exact_or_ulp(got, want, what):

@@ -28,6 +28,9 @@
 // tile is loaded under the S^T product and written out before the softmax, the next V tile is
 // loaded under the softmax / O^T product -- one barrier per tile.  Q (E/2 regs), O (E/2 regs)
 // live in the 512-entry unified register file (one wave per SIMD).
+//
+// Multi-head (nn.MultiheadAttention(E, H), ds_attention_h3_heads): the same kernels with a (sample, head) grid row and the head
+// width d = E / H as the template width; see MH below.
 #include <cstdlib>
 
 #include "ds_common.h"
@@ -67,11 +70,14 @@ __device__ __forceinline__ void split2(float a, float b, unsigned& hi, unsigned&
 
 __device__ __forceinline__ f16x8 as_f16x8(u32x4 v) { return __builtin_bit_cast(f16x8, v); }
 
-template <int ET, bool IMG>
+// MH (multi-head): grid.y runs over (sample, head) rows b * heads + h, E below is the head width d, and the head reads
+// rows [h d, (h+1) d) of each third of qkv [B, 3 heads d, L] and writes rows [h d, (h+1) d) of out [B, heads d, L].
+// MH = false is the single-head kernel exactly (heads = 1, nb = gridDim.y: the compiler sees the same code).
+template <int ET, bool IMG, bool MH>
 __global__ __launch_bounds__(NT) void k_attn3h(float* out, const float* __restrict__ qkv, const u32x4* __restrict__ kimg,
-                                               const u32x4* __restrict__ vimg, int L, float scale, float thr,
+                                               const u32x4* __restrict__ vimg, int L, int heads, int nb, float scale, float thr,
                                                const unsigned* in_amax, unsigned* out_amax) {
-  constexpr int E = 32 * ET;
+  constexpr int E = 32 * ET;                         // the head width
   constexpr int NDG = E / 8;                         // d-groups of 8
   constexpr int NS = E / 16;                         // k-slabs of the S^T product
   constexpr int KITEMS = NDG * KB;                   // (d-group, key) items per K tile
@@ -97,19 +103,22 @@ __global__ __launch_bounds__(NT) void k_attn3h(float* out, const float* __restri
     const unsigned xcd = id & 7u, k = id >> 3;
     const unsigned logical = xcd * per + (xcd < rem ? xcd : rem) + k;
     qblk = logical % nx;
-    b_u = logical / nx;
+    b_u = logical / nx;                              // the (sample, head) row
   }
-  const int b = (int)b_u;
+  const int row = (int)b_u;
+  const int b = MH ? row / heads : row, h = MH ? row - b * heads : 0;
+  const int Etot = MH ? E * heads : E;               // channels of one third of qkv
+  const int B = MH ? nb : (int)gridDim.y;
   const int q0_raw = ((int)qblk * 4 + wv) * 32;
   const bool active = q0_raw < L;                    // a wave past the last query block recomputes
   const int q0 = active ? q0_raw : L - 32;           // the last block and does not store (no branches
                                                      // around the MFMA pipeline: they cost registers)
-  const float* Qt = qkv + (size_t)b * 3 * E * L;
-  const float* Kt = Qt + (size_t)E * L;
-  const float* Vt = Kt + (size_t)E * L;
+  const float* Qt = qkv + ((size_t)b * 3 * Etot + (size_t)h * E) * L;
+  const float* Kt = Qt + (size_t)Etot * L;
+  const float* Vt = Kt + (size_t)Etot * L;
   // the sample's activation exponents (0 without in_amax): q, k times 2^ak, v times 2^av; S times 2^-2ak, O times 2^-av -- all exact
   const int ak = ds_epi::act_exponent_of(ds_epi::act_bits(in_amax, b), -60, 60);
-  const int av = ds_epi::act_exponent_of(ds_epi::act_bits(in_amax, (int)gridDim.y + b), -120, 120);
+  const int av = ds_epi::act_exponent_of(ds_epi::act_bits(in_amax, B + b), -120, 120);
   const float a_in = ds_epi::pow2f(ak), v_in = ds_epi::pow2f(av);
   const float s_un = ds_epi::pow2f(-2 * ak), o_un = ds_epi::pow2f(-av);
   scale = ds_epi::mul_pow2(scale, ak);
@@ -212,8 +221,8 @@ __global__ __launch_bounds__(NT) void k_attn3h(float* out, const float* __restri
   const int nkb = L / KB;
   // IMG: tile kb of sample b as LDS-ready images; a tile = KVEC (= VVEC = 8E) vectors = 2*ET 1-KiB pieces per wave
   static_assert(KVEC == VVEC && KVEC % (64 * 4) == 0, "image tiles are whole LDS-DMA pieces per wave");
-  const u32x4* kimg_b = IMG ? kimg + (size_t)b * nkb * KVEC : nullptr;
-  const u32x4* vimg_b = IMG ? vimg + (size_t)b * nkb * VVEC : nullptr;
+  const u32x4* kimg_b = IMG ? kimg + (size_t)row * nkb * KVEC : nullptr;
+  const u32x4* vimg_b = IMG ? vimg + (size_t)row * nkb * VVEC : nullptr;
   auto dma = [&](u32x4* dst, const u32x4* src) __attribute__((always_inline)) {
 #pragma unroll
     for (int i = 0; i < KVEC / 256; ++i) {
@@ -446,7 +455,7 @@ __global__ __launch_bounds__(NT) void k_attn3h(float* out, const float* __restri
   float amax = 0.f;
   if (active) {
     const float inv = (1.0f / l_run) * o_un;
-    float* ob = out + (size_t)b * E * L;
+    float* ob = out + ((size_t)b * Etot + (size_t)h * E) * L;
 #pragma unroll
     for (int t = 0; t < ET; ++t)
 #pragma unroll
@@ -463,18 +472,23 @@ __global__ __launch_bounds__(NT) void k_attn3h(float* out, const float* __restri
 // Pre-pass of the IMG form: one workgroup per (key tile, sample) writes the tile's K and V images
 //   K [piece][d-group][key 32][8 d]   V [piece][key-group][d][8 keys]        (the LDS layouts above)
 // with the split every attention workgroup would otherwise redo.  Reads K, V once (8 B/elt), writes as many bytes.
-template <int ET>
+// MH: one workgroup per (key tile, sample, head), images ordered by the (sample, head) row as the attention kernel reads them.
+template <int ET, bool MH>
 __global__ __launch_bounds__(NT) void k_attn_images(u32x4* __restrict__ kimg, u32x4* __restrict__ vimg,
-                                                   const float* __restrict__ qkv, int L, const unsigned* in_amax) {
+                                                   const float* __restrict__ qkv, int L, int heads, int nb,
+                                                   const unsigned* in_amax) {
   constexpr int E = 32 * ET, NDG = E / 8;
   constexpr int KITEMS = NDG * KB, VITEMS = E * 4;
-  const int tid = threadIdx.x, kb = blockIdx.x, b = blockIdx.y, nkb = L / KB;
+  const int tid = threadIdx.x, kb = blockIdx.x, row = blockIdx.y, nkb = L / KB;
+  const int b = MH ? row / heads : row, h = MH ? row - b * heads : 0;
+  const int Etot = MH ? E * heads : E;
+  const int B = MH ? nb : (int)gridDim.y;
   const float a_in = ds_epi::pow2f(ds_epi::act_exponent_of(ds_epi::act_bits(in_amax, b), -60, 60));       // the attention kernel's exponents
-  const float v_in = ds_epi::pow2f(ds_epi::act_exponent_of(ds_epi::act_bits(in_amax, (int)gridDim.y + b), -120, 120));
-  const float* Kt = qkv + ((size_t)b * 3 + 1) * E * L + (size_t)kb * KB;
-  const float* Vt = Kt + (size_t)E * L;
-  u32x4* Kd = kimg + ((size_t)b * nkb + kb) * (2 * KITEMS);
-  u32x4* Vd = vimg + ((size_t)b * nkb + kb) * (2 * VITEMS);
+  const float v_in = ds_epi::pow2f(ds_epi::act_exponent_of(ds_epi::act_bits(in_amax, B + b), -120, 120));
+  const float* Kt = qkv + (((size_t)b * 3 + 1) * Etot + (size_t)h * E) * L + (size_t)kb * KB;
+  const float* Vt = Kt + (size_t)Etot * L;
+  u32x4* Kd = kimg + ((size_t)row * nkb + kb) * (2 * KITEMS);
+  u32x4* Vd = vimg + ((size_t)row * nkb + kb) * (2 * VITEMS);
   for (int e = tid; e < KITEMS; e += NT) {
     const int dg = e / KB, key = e % KB;
     u32x4 h, l;
@@ -502,26 +516,28 @@ __global__ __launch_bounds__(NT) void k_attn_images(u32x4* __restrict__ kimg, u3
   }
 }
 
-template <int ET, bool IMG>
-int launch_attn3h(float* out, const float* qkv, void* workspace, int B, int L, float scale, const unsigned* in_amax,
+template <int ET, bool IMG, bool MH>
+int launch_attn3h(float* out, const float* qkv, void* workspace, int B, int heads, int L, float scale, const unsigned* in_amax,
                   unsigned* out_amax, hipStream_t s) {
-  constexpr int E = 32 * ET;
+  constexpr int E = 32 * ET;                                              // the head width
   const size_t lds = (size_t)2 * (2 * (E / 8) * KB + 2 * 4 * E) * 16;    // K and V, double-buffered
   if (lds > 48 * 1024) {
-    const int rc = ds::ensure_dynamic_lds<&k_attn3h<ET, IMG>>((int)lds, "hipFuncSetAttribute(attn3h)");
+    const int rc = ds::ensure_dynamic_lds<&k_attn3h<ET, IMG, MH>>((int)lds, "hipFuncSetAttribute(attn3h)");
     if (rc != DS_OK) return rc;
   }
+  const int rows = B * heads;                                             // (sample, head) rows
   u32x4* kimg = nullptr;
   u32x4* vimg = nullptr;
   if (IMG) {
     kimg = reinterpret_cast<u32x4*>(workspace);
-    vimg = kimg + (size_t)B * L * (E / 4);                                // K images: B * (L/32) tiles * 8E vectors
-    hipLaunchKernelGGL((k_attn_images<ET>), dim3(L / KB, B), dim3(NT), 0, s, kimg, vimg, qkv, L, in_amax);
+    vimg = kimg + (size_t)rows * L * (E / 4);                             // K images: rows * (L/32) tiles * 8E vectors
+    hipLaunchKernelGGL((k_attn_images<ET, MH>), dim3(L / KB, rows), dim3(NT), 0, s, kimg, vimg, qkv, L, heads, B, in_amax);
     DS_CHECK_LAUNCH("ds_attention_h3 (images)");
   }
-  dim3 g((L + 127) / 128, B);
+  dim3 g((L + 127) / 128, rows);
   static const float thr = [] { const char* e = getenv("DS_ATTN_T"); return e ? (float)atof(e) : RESCALE_T; }();   // diagnostic knob
-  hipLaunchKernelGGL((k_attn3h<ET, IMG>), g, dim3(NT), lds, s, out, qkv, kimg, vimg, L, scale, thr, in_amax, out_amax);
+  hipLaunchKernelGGL((k_attn3h<ET, IMG, MH>), g, dim3(NT), lds, s, out, qkv, kimg, vimg, L, heads, B, scale, thr, in_amax,
+                     out_amax);
   DS_CHECK_LAUNCH("ds_attention_h3");
   return DS_OK;
 }
@@ -540,14 +556,70 @@ int attention_h3(float* out, const float* qkv, void* workspace, int B, int E, in
   const float scale = (float)sqrt(1.0 / (double)E);
   hipStream_t s = ds::as_stream(stream);
   switch (E) {
-    case 32: return launch_attn3h<1, IMG>(out, qkv, workspace, B, L, scale, in_amax, out_amax, s);
-    case 64: return launch_attn3h<2, IMG>(out, qkv, workspace, B, L, scale, in_amax, out_amax, s);
-    case 128: return launch_attn3h<4, IMG>(out, qkv, workspace, B, L, scale, in_amax, out_amax, s);
-    case 256: return launch_attn3h<8, IMG>(out, qkv, workspace, B, L, scale, in_amax, out_amax, s);
+    case 32: return launch_attn3h<1, IMG, false>(out, qkv, workspace, B, 1, L, scale, in_amax, out_amax, s);
+    case 64: return launch_attn3h<2, IMG, false>(out, qkv, workspace, B, 1, L, scale, in_amax, out_amax, s);
+    case 128: return launch_attn3h<4, IMG, false>(out, qkv, workspace, B, 1, L, scale, in_amax, out_amax, s);
+    case 256: return launch_attn3h<8, IMG, false>(out, qkv, workspace, B, 1, L, scale, in_amax, out_amax, s);
     default:
       ds::set_error("ds_attention_h3: E=%d unsupported (32, 64, 128, 256)", E);
       return DS_ERR_UNSUPPORTED;
   }
+}
+
+bool mfma_head_width(int d) { return d == 32 || d == 64 || d == 128 || d == 256; }
+
+// Generic multi-head attention for head widths the MFMA tiling does not take (d not in {32, 64, 128, 256}) or sequence
+// lengths that are not a multiple of 32: one wave per (query, sample, head), exact fp32.  The scores are one
+// d-term FMA chain per key (lane = key); the softmax sum and every output channel are per-lane partial sums over the
+// keys lane, lane + 64, ... combined by a butterfly -- a correctness path, whose error stays near torch's at L = 4096.
+__global__ __launch_bounds__(64) void k_attn_heads_generic(float* out, const float* __restrict__ qkv, int d, int heads, int L,
+                                                           float scale) {
+  extern __shared__ float sm[];                      // [d] scaled query, then [L] probabilities
+  float* qs = sm;
+  float* ps = sm + d;
+  const int q = blockIdx.x, row = blockIdx.y, lane = threadIdx.x;
+  const int b = row / heads, h = row - b * heads, Etot = d * heads;
+  const float* Qt = qkv + ((size_t)b * 3 * Etot + (size_t)h * d) * L;
+  const float* Kt = Qt + (size_t)Etot * L;
+  const float* Vt = Kt + (size_t)Etot * L;
+  for (int c = lane; c < d; c += 64) qs[c] = Qt[(size_t)c * L + q] * scale;
+  __syncthreads();
+  float mx = -INFINITY;
+  for (int k = lane; k < L; k += 64) {
+    float sc = 0.f;
+    for (int c = 0; c < d; ++c) sc = fmaf(qs[c], Kt[(size_t)c * L + k], sc);
+    ps[k] = sc;
+    mx = fmaxf(mx, sc);
+  }
+  for (int o = 32; o > 0; o >>= 1) mx = fmaxf(mx, __shfl_xor(mx, o, 64));
+  float sum = 0.f;
+  for (int k = lane; k < L; k += 64) {
+    const float p = expf(ps[k] - mx);
+    ps[k] = p;
+    sum += p;
+  }
+  for (int o = 32; o > 0; o >>= 1) sum += __shfl_xor(sum, o, 64);
+  __syncthreads();
+  const float inv = 1.0f / sum;
+  float* ob = out + ((size_t)b * Etot + (size_t)h * d) * L;
+  for (int c = 0; c < d; ++c) {
+    const float* v = Vt + (size_t)c * L;
+    float acc = 0.f;
+    for (int k = lane; k < L; k += 64) acc = fmaf(ps[k], v[k], acc);
+    for (int o = 32; o > 0; o >>= 1) acc += __shfl_xor(acc, o, 64);
+    if (lane == 0) ob[(size_t)c * L + q] = acc * inv;
+  }
+}
+
+int heads_generic(float* out, const float* qkv, int B, int E, int heads, int L, hipStream_t s) {
+  const int d = E / heads;
+  const size_t lds = (size_t)(d + L) * sizeof(float);
+  DS_REQUIRE(lds <= 64 * 1024, DS_ERR_UNSUPPORTED, "ds_attention_heads_generic: d + L = %d is too large for the generic path", d + L);
+  if (B == 0) return DS_OK;
+  const float scale = (float)sqrt(1.0 / (double)d);
+  hipLaunchKernelGGL(k_attn_heads_generic, dim3(L, B * heads), dim3(64), lds, s, out, qkv, d, heads, L, scale);
+  DS_CHECK_LAUNCH("ds_attention_heads_generic");
+  return DS_OK;
 }
 
 }  // namespace
@@ -565,4 +637,56 @@ extern "C" size_t ds_attention_h3_workspace_bytes(int B, int E, int L) {
 extern "C" int ds_attention_h3_ws(float* out, const float* qkv, void* workspace, int B, int E, int L, const unsigned* in_amax,
                                   unsigned* out_amax, void* stream) {
   return attention_h3<true>(out, qkv, workspace, B, E, L, in_amax, out_amax, stream);
+}
+
+extern "C" size_t ds_attention_h3_heads_workspace_bytes(int B, int E, int heads, int L) {
+  if (B <= 0 || E <= 0 || L <= 0 || heads <= 0 || E % heads || !mfma_head_width(E / heads) || L % 32) return 0;
+  return (size_t)B * L * E * 8;                      // the images of every (sample, head) row: as many bytes as one head of E
+}
+
+extern "C" int ds_attention_h3_heads(float* out, const float* qkv, void* workspace, int B, int E, int heads, int L,
+                                     const unsigned* in_amax, unsigned* out_amax, void* stream) {
+  DS_REQUIRE(out && qkv, DS_ERR_NULL, "ds_attention_h3_heads: NULL pointer");
+  DS_REQUIRE(B >= 0 && E > 0 && L > 0 && heads > 0, DS_ERR_SHAPE, "ds_attention_h3_heads: bad shape B=%d E=%d heads=%d L=%d",
+             B, E, heads, L);
+  DS_REQUIRE(E % heads == 0, DS_ERR_SHAPE, "ds_attention_h3_heads: E=%d is not a multiple of heads=%d", E, heads);
+  DS_REQUIRE((size_t)B * heads < 65536, DS_ERR_SHAPE, "ds_attention_h3_heads: B*heads=%lld exceeds grid.y", (long long)B * heads);
+  if (heads == 1) {                                  // the single-head entry points, unchanged
+    if (workspace) return attention_h3<true>(out, qkv, workspace, B, E, L, in_amax, out_amax, stream);
+    return attention_h3<false>(out, qkv, nullptr, B, E, L, in_amax, out_amax, stream);
+  }
+  if (B == 0) return DS_OK;
+  const int d = E / heads;
+  const float scale = (float)sqrt(1.0 / (double)d);
+  hipStream_t s = ds::as_stream(stream);
+  if (!mfma_head_width(d) || L % 32) {
+    DS_REQUIRE(out_amax == nullptr, DS_ERR_UNSUPPORTED,
+               "ds_attention_h3_heads: out_amax needs a head width in {32, 64, 128, 256} and L a multiple of 32 (reduce with "
+               "ds_absmax_rows instead)");
+    return heads_generic(out, qkv, B, E, heads, L, s);
+  }
+  DS_REQUIRE((reinterpret_cast<uintptr_t>(qkv) & 15u) == 0, DS_ERR_SHAPE, "ds_attention_h3_heads: qkv must be 16-byte aligned");
+  DS_REQUIRE(!workspace || (reinterpret_cast<uintptr_t>(workspace) & 15u) == 0, DS_ERR_SHAPE,
+             "ds_attention_h3_heads: the workspace must be 16-byte aligned");
+  const bool img = workspace != nullptr;
+  switch (d) {
+    case 32: return img ? launch_attn3h<1, true, true>(out, qkv, workspace, B, heads, L, scale, in_amax, out_amax, s)
+                        : launch_attn3h<1, false, true>(out, qkv, nullptr, B, heads, L, scale, in_amax, out_amax, s);
+    case 64: return img ? launch_attn3h<2, true, true>(out, qkv, workspace, B, heads, L, scale, in_amax, out_amax, s)
+                        : launch_attn3h<2, false, true>(out, qkv, nullptr, B, heads, L, scale, in_amax, out_amax, s);
+    case 128: return img ? launch_attn3h<4, true, true>(out, qkv, workspace, B, heads, L, scale, in_amax, out_amax, s)
+                         : launch_attn3h<4, false, true>(out, qkv, nullptr, B, heads, L, scale, in_amax, out_amax, s);
+    default: return img ? launch_attn3h<8, true, true>(out, qkv, workspace, B, heads, L, scale, in_amax, out_amax, s)
+                        : launch_attn3h<8, false, true>(out, qkv, nullptr, B, heads, L, scale, in_amax, out_amax, s);
+  }
+}
+
+extern "C" int ds_attention_heads_generic(float* out, const float* qkv, int B, int E, int heads, int L, void* stream) {
+  DS_REQUIRE(out && qkv, DS_ERR_NULL, "ds_attention_heads_generic: NULL pointer");
+  DS_REQUIRE(B >= 0 && E > 0 && L > 0 && heads > 0, DS_ERR_SHAPE, "ds_attention_heads_generic: bad shape B=%d E=%d heads=%d L=%d",
+             B, E, heads, L);
+  DS_REQUIRE(E % heads == 0, DS_ERR_SHAPE, "ds_attention_heads_generic: E=%d is not a multiple of heads=%d", E, heads);
+  DS_REQUIRE((size_t)B * heads < 65536, DS_ERR_SHAPE, "ds_attention_heads_generic: B*heads=%lld exceeds grid.y",
+             (long long)B * heads);
+  return heads_generic(out, qkv, B, E, heads, L, ds::as_stream(stream));
 }

@@ -152,8 +152,10 @@ class ADMBaseBlock(torch.nn.Module):
             bad.append("conv_type 'default' or 'circular'")
         if first_norm not in ("GroupLN", "GroupRMS") or second_norm not in ("GroupLN", "GroupRMS"):
             bad.append("norms 'GroupLN' or 'GroupRMS'")
-        if num_groups != 1 or image_sample_factor != 2 or attn_heads != 1 or attn_type != "default":
-            bad.append("num_groups=1, image_sample_factor=2, one default attention head")
+        if num_groups != 1 or image_sample_factor != 2 or (attn_type != "default" and attn_heads == 1):
+            bad.append("num_groups=1, image_sample_factor=2, default attention")
+        if attn_type != "default" and attn_heads != 1:
+            bad.append(f"attn_heads={attn_heads} with attn_type 'default' only (attn_type={attn_type!r} takes one head)")
         if image_sample not in (None, "downsample", "upsample"):
             bad.append("image_sample None, 'downsample' or 'upsample'")
         if image_sample == "downsample" and image_sample_type not in (None, "avg"):
@@ -164,6 +166,9 @@ class ADMBaseBlock(torch.nn.Module):
             bad.append("skip_integration_type 'concat' or 'add'")
         if bad:
             raise NotImplementedError("diffsci_amd ADM blocks support: " + "; ".join(bad))
+        if has_attn and (attn_heads < 1 or channels_out % attn_heads):      # torch.nn.MultiheadAttention's own rule
+            raise ValueError(f"attn_heads={attn_heads} must divide channels_out={channels_out}")
+        self.attn_heads = attn_heads
         self.channels_in, self.channels_out, self.channels_embed = channels_in, channels_out, channels_embed
         self.channels_skip, self.dimension, self.image_sample = channels_skip, dimension, image_sample
         self.has_residual, self.has_attn, self.attn_residual = has_residual, has_attn, attn_residual
@@ -182,7 +187,7 @@ class ADMBaseBlock(torch.nn.Module):
         if has_residual:
             self.convresidual = make_conv(cin, channels_out, 1, circ, True, dimension)
         if has_attn:
-            self.attn = _Attn(channels_out)
+            self.attn = _Attn(channels_out, heads=attn_heads)
         self.conv_precision = "fp16x3"
         self._packed, self._packed_sig = None, None
 
@@ -277,7 +282,7 @@ class ADMBaseBlock(torch.nn.Module):
             E, L = Co, out.numel() // (B * Co)
             mh = self.attn.mhattn
             qkv = ops.conv(v4(out), pk["in"], bias=mh.in_proj_bias)
-            o = ops.attention(qkv.view(B, 3 * E, L), E, precision=self.conv_precision)
+            o = ops.attention(qkv.view(B, 3 * E, L), E, precision=self.conv_precision, heads=mh.num_heads)
             out = ops.conv(o.view(v4(out).shape), pk["out"], bias=mh.out_proj.bias,
                            res1=v4(out) if self.attn_residual else None).view(out.shape)
         return out
@@ -860,10 +865,10 @@ class ADM(torch.nn.Module):
         if h3 and not split:
             ops.absmax_rows(qkv[:, :2 * E], out=a_qkv[:B])
             ops.absmax_rows(qkv[:, 2 * E:], out=a_qkv[B:])
-        nws = ops.attention_workspace_floats(B, E, L, self.conv_precision)
+        nws = ops.attention_workspace_floats(B, E, L, self.conv_precision, heads=m.num_heads)
         aws = ws.take((nws,), x.device) if nws else None
         o = ops.attention(qkv.view(B, 3 * E, L), E, out=ws.take((B, E, L), x.device),
-                          precision=self.conv_precision, workspace=aws, **akw(in_amax=a_qkv, out_amax=a_o))
+                          precision=self.conv_precision, workspace=aws, heads=m.num_heads, **akw(in_amax=a_qkv, out_amax=a_o))
         if aws is not None:
             ws.give(aws)
         y = ops.conv(o.view(B, E, Hh, Ww), pk[(id(att), "out")], bias=m.out_proj.bias,

@@ -167,10 +167,10 @@ class _Sampler(torch.nn.Module):
 
 
 class _Attn(torch.nn.Module):
-    def __init__(self, C, mp=False, cosine=False):
+    def __init__(self, C, mp=False, cosine=False, heads=1):
         super().__init__()
         self.mhattn = (_InHouseAttention(C, mp, cosine) if (mp or cosine)
-                       else torch.nn.MultiheadAttention(C, num_heads=1, batch_first=True))
+                       else torch.nn.MultiheadAttention(C, num_heads=heads, batch_first=True))
 
 
 class _Fourier(torch.nn.Module):

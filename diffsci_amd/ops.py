@@ -1069,23 +1069,41 @@ def _attention_uses_images(E, L, precision):
     return L >= ATTN_IMAGES_MIN_L or (E == 256 and L >= ATTN_IMAGES_MIN_L_WIDE)
 
 
-def attention_workspace_floats(B, E, L, precision="fp16x3"):
+def _check_heads(E, heads):
+    heads = int(heads)
+    if heads < 1 or E % heads:
+        raise ValueError(f"attention: E={E} is not a multiple of heads={heads}")
+    return heads
+
+
+def attention_workspace_floats(B, E, L, precision="fp16x3", heads=1):
     """Floats of scratch attention() can use (0: none) -- for callers that keep buffers in a pool."""
+    heads = _check_heads(E, heads)
+    if heads > 1:       # the image form by the head width: a head's K / V tiles are re-split once per 128 of its queries
+        if _attention_uses_images(E // heads, L, precision):
+            return N.lib().ds_attention_h3_heads_workspace_bytes(B, E, heads, L) // 4
+        return 0
     if _attention_uses_images(E, L, precision):
         return N.lib().ds_attention_h3_workspace_bytes(B, E, L) // 4
     return 0
 
 
-def attention(qkv, E, out=None, precision="fp32", workspace=None, in_amax=None, out_amax=None):
+def attention(qkv, E, out=None, precision="fp32", workspace=None, in_amax=None, out_amax=None, heads=1):
     """qkv [B, 3E, L] channel-major -> out [B, E, L].  precision "fp16x3": split-fp16 MFMA
     (fp32-level accuracy, E <= 256); anything else, or wider heads: exact-fp32 MFMA.
     workspace: float tensor of attention_workspace_floats(...) elements; allocated here when needed and not given.
     in_amax: int32 [2, B] -- per-sample max |q, k| and max |v| (conv2d(..., amax_split=2E) leaves them), None = reduced here;
     out_amax [B]: as conv2d.  The fp16x3 kernels stage q, k and v times the sample's powers of two; the exact-fp32 kernels need
-    none, and an out_amax request is served by a reduction over their result."""
+    none, and an out_amax request is served by a reduction over their result.
+    heads: nn.MultiheadAttention(E, heads) -- E % heads == 0; head h attends over rows [h d, (h+1) d) of each third of qkv,
+    d = E / heads, with logits scaled by 1/sqrt(d).  fp16x3 at d in {32, 64, 128, 256} and L % 32 == 0: the split-fp16 kernel
+    with a head axis; any other d or L, or precision "fp32": the exact-fp32 per-head kernel.  heads=1 is the single-head call."""
     B, E3, L = qkv.shape
     if E3 != 3 * E:
         raise ValueError("qkv must be [B, 3E, L]")
+    heads = _check_heads(E, heads)
+    if heads > 1:
+        return _attention_heads(qkv, E, heads, out, precision, workspace, in_amax, out_amax)
     if out is None:
         out = torch.empty((B, E, L), dtype=torch.float32, device=qkv.device)
     h3 = precision == "fp16x3" and L % 32 == 0 and E in (32, 64, 128, 256)
@@ -1110,6 +1128,32 @@ def attention(qkv, E, out=None, precision="fp32", workspace=None, in_amax=None, 
             N.check(N.lib().ds_attention_generic(_p(out), _p(qkv), B, E, L, _stream()), "ds_attention_generic")
         else:
             N.check(N.lib().ds_attention(_p(out), _p(qkv), B, E, L, _stream()), "ds_attention")
+        if out_amax is not None:
+            absmax_rows(out, B, out=out_amax)
+    return out
+
+
+def _attention_heads(qkv, E, heads, out, precision, workspace, in_amax, out_amax):
+    B, _, L = qkv.shape
+    if out is None:
+        out = torch.empty((B, E, L), dtype=torch.float32, device=qkv.device)
+    d = E // heads
+    if precision == "fp16x3" and L % 32 == 0 and d in (32, 64, 128, 256):
+        if in_amax is None:          # one exponent pair per sample serves all its heads
+            in_amax = amax_new(2 * B, qkv.device)
+            absmax_rows(qkv[:, :2 * E], out=in_amax[:B])
+            absmax_rows(qkv[:, 2 * E:], out=in_amax[B:])
+        pin, pout = (None if in_amax is NORMALISED else _pi(in_amax, 2 * B, "in_amax")), _pi(out_amax, B, "out_amax")
+        need = attention_workspace_floats(B, E, L, precision, heads)
+        if need and workspace is None:
+            workspace = torch.empty(need, dtype=torch.float32, device=qkv.device)
+        elif need and workspace.numel() < need:
+            raise ValueError("attention workspace too small")
+        pws = _p(workspace, "workspace") if need else None
+        N.check(N.lib().ds_attention_h3_heads(_p(out), _p(qkv), pws, B, E, heads, L, pin, pout, _stream()),
+                "ds_attention_h3_heads")
+    else:
+        N.check(N.lib().ds_attention_heads_generic(_p(out), _p(qkv), B, E, heads, L, _stream()), "ds_attention_heads_generic")
         if out_amax is not None:
             absmax_rows(out, B, out=out_amax)
     return out

@@ -442,6 +442,20 @@ int ds_attention_h3(float* out, const float* qkv, int B, int E, int L, const uns
 size_t ds_attention_h3_workspace_bytes(int B, int E, int L);
 int ds_attention_h3_ws(float* out, const float* qkv, void* workspace, int B, int E, int L, const unsigned* in_amax,
                        unsigned* out_amax, void* stream);
+/* Multi-head self-attention (nn.MultiheadAttention(E, num_heads = heads) core): E % heads == 0, head width d = E / heads.
+ * Same channel-major operands: head h reads rows [h d, (h+1) d) of each third of qkv [B, 3E, L] and writes rows
+ * [h d, (h+1) d) of out [B, E, L]; logits scaled by 1 / sqrt(d).  d in {32, 64, 128, 256} and L a multiple of 32: the
+ * fp16x3 kernel of ds_attention_h3 with one workgroup per (sample, head, 128 queries), in_amax / out_amax as there (a
+ * sample's exponents serve all its heads); workspace NULL stages in every workgroup, otherwise it holds
+ * ds_attention_h3_heads_workspace_bytes(B, E, heads, L) bytes (16-byte aligned) of K / V images.  Any other d or L: an exact
+ * fp32 path, one wave per (query, sample, head) (workspace and in_amax unused; out_amax must be NULL).  heads = 1 is
+ * ds_attention_h3 / ds_attention_h3_ws. */
+size_t ds_attention_h3_heads_workspace_bytes(int B, int E, int heads, int L);
+int ds_attention_h3_heads(float* out, const float* qkv, void* workspace, int B, int E, int heads, int L, const unsigned* in_amax,
+                          unsigned* out_amax, void* stream);
+/* The exact-fp32 multi-head path alone, for any E % heads == 0 and L (d + L <= 16384): one wave per (query, sample, head),
+ * fp32 FMA chains, per-lane partial sums over the keys combined by a butterfly.  Same operands and result contract. */
+int ds_attention_heads_generic(float* out, const float* qkv, int B, int E, int heads, int L, void* stream);
 
 /* y[m, n] = act(sum_k x[m,k]*w[n,k] + b[n]); act 0 none, 1 SiLU, 2 ReLU.  torch Linear layout.
  * ResnetTimeBlock (commonlayers.py:516-522) and MLPUncond (mlp.py:30-37). b may be NULL. */

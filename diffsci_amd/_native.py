@@ -88,6 +88,8 @@ _PROTOS = {
     "ds_slice_tables": (c_int, [_P, _P, _P, _P, c_int, c_int, c_int, c_int, c_longlong, c_float, c_int, c_int, _P]),
     "ds_avgpool3d": (c_int, [_P, _P, c_int, c_int, c_int, c_int, _P]),
     "ds_upsample3d": (c_int, [_P, _P, c_int, c_int, c_int, c_int, _P]),
+    "ds_avgpool3d_f": (c_int, [_P, _P, c_int, c_int, c_int, c_int, c_int, _P]),
+    "ds_upsample_f": (c_int, [_P, _P, c_int, c_int, c_int, c_int, c_int, c_int, _P]),
     "ds_conv1x1_h3_packed_bytes": (c_size_t, [c_int, c_int]),
     "ds_conv1x1_h3_pack_weights": (c_int, [_P, _P, c_int, c_int, c_int, _P]),
     "ds_conv1x1_h3": (c_int, [_P, _P, _P, c_int, _P, _P, c_int, _P, _P, c_int, c_int, c_int, c_int, c_int, c_int, _P, _P, _P, c_int, _P]),
@@ -106,6 +108,7 @@ _PROTOS = {
     "ds_gnorm1_workspace_bytes": (c_size_t, [c_int]),
     "ds_gnorm1_stats": (c_int, [_P, _P, _P, c_int, c_int, c_int, c_float, c_int, _P]),
     "ds_gnorm1_apply": (c_int, [_P, _P, _P, _P, _P, _P, _P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, _P]),
+    "ds_gnorm1_apply_poolf": (c_int, [_P, _P, _P, _P, _P, _P, _P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, _P]),
     "ds_concat2": (c_int, [_P, _P, _P, c_int, c_size_t, c_size_t, _P]),
     "ds_add_act": (c_int, [_P, _P, _P, c_int, c_int, c_int, c_int, _P]),
     "ds_mask_blend": (c_int, [_P, _P, _P, _P, c_size_t, c_int, _P]),

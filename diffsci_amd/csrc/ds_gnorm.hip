@@ -9,6 +9,7 @@
 //       kind 1:  SiLU((x/denom*w[c] + b[c])*te1[b,c] + te2[b,c])           norm2 -> FiLM -> act
 //       kind 2:  x                                                         (residual branch input)
 //     followed, when pool = 1, by the block's 2x2 average pooling (adm.py:316-319, 345-347).
+//   ds_gnorm1_apply_poolf  the same followed by an f x f average pooling, any f >= 1 (image_sample_factor != 2).
 #include "ds_common.h"
 
 namespace {
@@ -154,6 +155,47 @@ __global__ __launch_bounds__(NT) void k_g1_apply(float* out, const float* __rest
   }
 #undef DS_P
 #undef DS_A
+}
+
+// k_g1_apply followed by AvgPool2d(f) for any factor f >= 1 (image_sample_factor != 2, adm.py:361-383): one thread = one output
+// pixel of one (b, c) row.  The f x f window is summed in torch avg_pool2d's order (rows, then columns, from 0) and divided by
+// f^2 once, as k_g1_apply does for f = 2; rows and columns past f * (H / f), f * (W / f) are dropped (floor output size).
+// VLOAD: f and W multiples of 4, x 16-byte aligned -- each window row is f/4 float4 loads.
+template <int KIND, bool VLOAD>
+__global__ __launch_bounds__(NT) void k_g1_apply_poolf(float* out, const float* __restrict__ x, const float* __restrict__ stats,
+                                                       const float* __restrict__ w, const float* __restrict__ bias,
+                                                       const float* __restrict__ film1, const float* __restrict__ film2,
+                                                       int film_stride, unsigned C, int H, int W, unsigned Ho, unsigned Wo, int f,
+                                                       unsigned total) {
+  const float div = (float)(f * f);
+  for (unsigned i = blockIdx.x * NT + threadIdx.x; i < total; i += gridDim.x * NT) {     // 32-bit indices: the host checks total
+    const unsigned xo = i % Wo, t = i / Wo;
+    const unsigned yo = t % Ho, bc = t / Ho;
+    const int c = (int)(bc % C), b = (int)(bc / C);
+    const float mean = KIND == 2 ? 0.f : stats[2 * b], sd = KIND == 2 ? 1.f : stats[2 * b + 1];
+    const float wc = (KIND == 2 || !w) ? 1.f : w[c], bc_ = (KIND == 2 || !bias) ? 0.f : bias[c];
+    float f1 = 1.f, f2 = 0.f;
+    const bool film = KIND != 2 && film1 != nullptr;
+    if (film) {
+      f1 = film1[(size_t)b * film_stride + c];
+      f2 = film2[(size_t)b * film_stride + c];
+    }
+#define DS_A(v) apply1<KIND>(v, mean, sd, wc, bc_, film, f1, f2)
+    const float* r = x + ((size_t)bc * H + (size_t)yo * f) * W + (size_t)xo * f;
+    float s = 0.f;
+    for (int dy = 0; dy < f; ++dy, r += W) {
+      if (VLOAD) {
+        for (int dx = 0; dx < f; dx += 4) {
+          const float4 v = *reinterpret_cast<const float4*>(r + dx);
+          s = s + DS_A(v.x); s = s + DS_A(v.y); s = s + DS_A(v.z); s = s + DS_A(v.w);
+        }
+      } else {
+        for (int dx = 0; dx < f; ++dx) s = s + DS_A(r[dx]);
+      }
+    }
+#undef DS_A
+    out[i] = s / div;
+  }
 }
 
 // k_g1_apply with the result written as the consuming convolution's pre-split fp16 hi / lo images (ds_conv2d_h3_img; layout and
@@ -342,6 +384,37 @@ int ds_gnorm1_apply(float* out, const float* x, const float* stats, const float*
 #undef LV
 #undef L
   DS_CHECK_LAUNCH("ds_gnorm1_apply");
+  return DS_OK;
+}
+
+int ds_gnorm1_apply_poolf(float* out, const float* x, const float* stats, const float* w, const float* b,
+                          const float* film_scale, const float* film_shift, int film_stride, int B, int C, int H, int W,
+                          int kind, int factor, void* stream) {
+  DS_REQUIRE(out && x, DS_ERR_NULL, "ds_gnorm1_apply_poolf: NULL pointer");
+  DS_REQUIRE(kind >= 0 && kind <= 2, DS_ERR_UNSUPPORTED, "ds_gnorm1_apply_poolf: kind %d", kind);
+  DS_REQUIRE(kind == 2 || stats, DS_ERR_NULL, "ds_gnorm1_apply_poolf: stats is NULL");
+  DS_REQUIRE((film_scale == nullptr) == (film_shift == nullptr), DS_ERR_NULL, "ds_gnorm1_apply_poolf: FiLM scale and shift go together");
+  DS_REQUIRE(B >= 0 && C > 0 && H > 0 && W > 0, DS_ERR_SHAPE, "ds_gnorm1_apply_poolf: bad shape");
+  DS_REQUIRE(factor >= 1 && factor <= H && factor <= W, DS_ERR_SHAPE,
+             "ds_gnorm1_apply_poolf: factor %d must be in [1, min(H, W)] (H=%d W=%d)", factor, H, W);
+  if (B == 0) return DS_OK;
+  const int Ho = H / factor, Wo = W / factor;
+  const size_t total = (size_t)B * C * Ho * Wo;
+  DS_REQUIRE(total < (1ull << 32) - 2048ull * NT, DS_ERR_SHAPE, "ds_gnorm1_apply_poolf: output too large (%zu floats)", total);
+  const bool vload = factor % 4 == 0 && W % 4 == 0 && (reinterpret_cast<uintptr_t>(x) & 15u) == 0;
+  size_t g = (total + NT - 1) / NT;
+  if (g > 2048) g = 2048;                                  // grid-stride the rest
+  hipStream_t s = ds::as_stream(stream);
+#define L(K, V) hipLaunchKernelGGL((k_g1_apply_poolf<K, V>), dim3((unsigned)g), dim3(NT), 0, s, out, x, stats, w, b, film_scale, \
+                                   film_shift, film_stride, (unsigned)C, H, W, (unsigned)Ho, (unsigned)Wo, factor, \
+                                   (unsigned)total)
+#define LV(K) do { if (vload) L(K, true); else L(K, false); } while (0)
+  if (kind == 0) LV(0);
+  else if (kind == 1) LV(1);
+  else LV(2);
+#undef LV
+#undef L
+  DS_CHECK_LAUNCH("ds_gnorm1_apply_poolf");
   return DS_OK;
 }
 

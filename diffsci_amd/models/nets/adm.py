@@ -2,14 +2,15 @@
 
 Same constructor, ``net(x, t, y=None)`` protocol and state_dict key names as the reference's
 ``ADM`` / ``ADMConfig`` (adm.py:8-216), for the default family: 2-D fields, default convolutions,
-GroupLN(1 group) + GroupRMS(1 group) norms, avg-pool down / nearest up inside the last block of a
-layer, decoder_type 1 or 2, single-head attention in the middle block.  The torch.nn layers are
+GroupLN(1 group) + GroupRMS(1 group) norms, avg-pool down / nearest up by transition_scale_factor inside the
+last block of a layer, decoder_type 1 or 2, single-head attention in the middle block.  The torch.nn layers are
 parameter containers only; every tensor operation is a launch into libdiffsci_hip.so:
 
   input/output layer, conv1 (+nearest-up load), conv2 (+residual)   ds_conv2d*
   convresidual (1x1, +nearest-up load)                              ds_conv2d
   GroupNorm(1,C)+SiLU [+AvgPool2d], GroupRMSNorm(1,C)+FiLM+SiLU      ds_gnorm1_stats, ds_gnorm1_apply
   AvgPool2d on the residual branch                                  ds_gnorm1_apply (kind 2)
+  resampling by a factor other than 2                               ds_gnorm1_apply_poolf, ds_upsample_f
   skip concat / add                                                 ds_concat2 / ds_add
   ADMTimeEmbedding, embed_linear                                    ds_fourier_features, ds_linear, ds_add_act
   attention                                                         ds_conv2d (1x1) + ds_attention*
@@ -95,7 +96,7 @@ class ADMConfig(object):
              "first/second_resblock_norm 'GroupLN' or 'GroupRMS' (the reference raises on anything else, adm.py:395,406)"),
             (self.num_groups == 1, "num_groups=1"),
             (self.kernel_size == 3, "kernel_size=3"),
-            (self.transition_scale_factor == 2, "transition_scale_factor=2"),
+            (_is_factor(self.transition_scale_factor), "an integer transition_scale_factor >= 1"),
             (self.decoder_type in (1, 2), "decoder_type 1 or 2"),
             (self.skip_integration_type in ("concat", "add"), "skip_integration_type 'concat' or 'add'"),
             (self.number_resnet_downward_block >= 1 and self.number_resnet_upward_block >= 1,
@@ -105,13 +106,36 @@ class ADMConfig(object):
         return None if not bad else "diffsci_amd ADM supports: " + "; ".join(bad)
 
 
+def _is_factor(f):
+    try:
+        resample_factor(f, "")
+        return True
+    except ValueError:
+        return False
+
+
+def resample_factor(f, what):
+    """An ADM resampling factor (image_sample_factor / downsample_factor / upsample_factor / transition_scale_factor) as an
+    int >= 1: AvgPool(kernel_size=f) down, Upsample(scale_factor=f, mode='nearest') up."""
+    ok = not isinstance(f, bool) and isinstance(f, (int, float)) and f == f and float(f).is_integer() and f >= 1
+    if not ok:
+        try:
+            import operator
+            ok, f = operator.index(f) >= 1, operator.index(f)            # integer numpy scalars
+        except TypeError:
+            ok = False
+    if not ok:
+        raise ValueError(f"{what}={f!r}: diffsci_amd ADM resamples by an integer factor >= 1")
+    return int(f)
+
+
 class _Block(torch.nn.Module):
-    """ADMBaseBlock parameters (adm.py:262-287); sample in {None, 'down', 'up'}."""
+    """ADMBaseBlock parameters (adm.py:262-287); sample in {None, 'down', 'up'}, by `factor`."""
 
     def __init__(self, cin, cout, cembed, sample=None, has_attn=False, circular=False,
-                 norms=("GroupLN", "GroupRMS"), affine=True):
+                 norms=("GroupLN", "GroupRMS"), affine=True, factor=2):
         super().__init__()
-        self.cin, self.cout, self.sample = cin, cout, sample
+        self.cin, self.cout, self.sample, self.factor = cin, cout, sample, factor
         # make_norm_layers, adm.py:385-406 (num_groups = 1): GroupNorm(1, C) or GroupRMSNorm(1, C) in either slot
         self.norm1 = torch.nn.GroupNorm(1, cin, affine=affine) if norms[0] == "GroupLN" else _AffineHolder(cin, affine)
         self.norm2 = torch.nn.GroupNorm(1, cout, affine=affine) if norms[1] == "GroupLN" else _AffineHolder(cout, affine)
@@ -152,8 +176,8 @@ class ADMBaseBlock(torch.nn.Module):
             bad.append("conv_type 'default' or 'circular'")
         if first_norm not in ("GroupLN", "GroupRMS") or second_norm not in ("GroupLN", "GroupRMS"):
             bad.append("norms 'GroupLN' or 'GroupRMS'")
-        if num_groups != 1 or image_sample_factor != 2 or (attn_type != "default" and attn_heads == 1):
-            bad.append("num_groups=1, image_sample_factor=2, default attention")
+        if num_groups != 1 or (attn_type != "default" and attn_heads == 1):
+            bad.append("num_groups=1, default attention")
         if attn_type != "default" and attn_heads != 1:
             bad.append(f"attn_heads={attn_heads} with attn_type 'default' only (attn_type={attn_type!r} takes one head)")
         if image_sample not in (None, "downsample", "upsample"):
@@ -166,9 +190,11 @@ class ADMBaseBlock(torch.nn.Module):
             bad.append("skip_integration_type 'concat' or 'add'")
         if bad:
             raise NotImplementedError("diffsci_amd ADM blocks support: " + "; ".join(bad))
+        factor = resample_factor(image_sample_factor, "image_sample_factor")
         if has_attn and (attn_heads < 1 or channels_out % attn_heads):      # torch.nn.MultiheadAttention's own rule
             raise ValueError(f"attn_heads={attn_heads} must divide channels_out={channels_out}")
         self.attn_heads = attn_heads
+        self.image_sample_factor = factor
         self.channels_in, self.channels_out, self.channels_embed = channels_in, channels_out, channels_embed
         self.channels_skip, self.dimension, self.image_sample = channels_skip, dimension, image_sample
         self.has_residual, self.has_attn, self.attn_residual = has_residual, has_attn, attn_residual
@@ -257,18 +283,35 @@ class ADMBaseBlock(torch.nn.Module):
         film = ops.linear(te.to(x).contiguous(), self.embed_linear.weight, self.embed_linear.bias)      # [B or 1, 2*Cout]
         # first_block (adm.py:315-322): norm1 -> act -> resample -> conv1
         st = ops.gnorm1_stats(x, k1, eps=1e-5)
-        fuse_pool = down and self.dimension == 2
-        a = ops.gnorm1_apply(v4(x), st, self.norm1.weight, self.norm1.bias, k1, pool=fuse_pool)
-        if down and self.dimension == 3:
-            a = ops.avgpool3d(a.view(x.shape))
-        elif self.dimension == 3:
-            a = a.view(x.shape)
-        y = self._conv3(self.conv1, a, pk, up=up)
+        f = self.image_sample_factor
+        if (down or up) and f != 2:
+            # any other factor: the norm pass pools by f itself (fields) or is followed by the resampling kernel, then a
+            # plain conv1 -- the fused x2 loaders stay the factor-2 route
+            if down and self.dimension == 2:
+                a = ops.gnorm1_apply_poolf(x, st, self.norm1.weight, self.norm1.bias, k1, f)
+            else:
+                a = ops.gnorm1_apply(v4(x), st, self.norm1.weight, self.norm1.bias, k1).view(x.shape)
+                a = ops.avgpool_f(a, f) if down else ops.upsample_f(a, f)
+            y = self._conv3(self.conv1, a, pk)
+        else:
+            fuse_pool = down and self.dimension == 2
+            a = ops.gnorm1_apply(v4(x), st, self.norm1.weight, self.norm1.bias, k1, pool=fuse_pool)
+            if down and self.dimension == 3:
+                a = ops.avgpool3d(a.view(x.shape))
+            elif self.dimension == 3:
+                a = a.view(x.shape)
+            y = self._conv3(self.conv1, a, pk, up=up)
         # norm2 -> FiLM -> act -> conv2 (adm.py:306-308,324-329)
         st2 = ops.gnorm1_stats(y, k2, eps=1e-5)
         a2 = ops.gnorm1_apply(v4(y), st2, self.norm2.weight, self.norm2.bias, k2, film=film).view(y.shape)
         r = None
-        if self.has_residual:                        # convresidual(resample(x)), adm.py:345-349
+        if self.has_residual and (down or up) and f != 2:
+            m = self.convresidual
+            xr = ops.avgpool_f(x, f) if down else x
+            r = ops.conv(v4(xr), pk[id(m)], bias=m.bias).view((B, Co) + tuple(xr.shape[2:]))
+            if up:                                   # a 1x1 convolution commutes with nearest upsampling: project at low resolution
+                r = ops.upsample_f(r, f)
+        elif self.has_residual:                      # convresidual(resample(x)), adm.py:345-349
             xr = pool(x) if down else x
             m = self.convresidual
             if up and self.dimension == 2:           # nearest x2 in the 1x1 convolution's loader
@@ -575,11 +618,12 @@ class ADM(torch.nn.Module):
         # not forward it, adm.py:455-520,540-834): the norms are always affine, and checkpoints carry their weights
         nk = dict(norms=(config.first_resblock_norm, config.second_resblock_norm))
         nb = config.number_resnet_downward_block
+        tf = resample_factor(config.transition_scale_factor, "transition_scale_factor")
         enc = []
         for i in range(len(mult) - 1):                                   # adm.py:566-592
             cin, cout = mc * mult[i], mc * mult[i + 1]
             enc.append(_Layer([_Block(cin, cin, ce, circular=circ, **nk) for _ in range(nb - 1)] +
-                              [_Block(cin, cout, ce, "down", circular=circ, **nk)]))
+                              [_Block(cin, cout, ce, "down", circular=circ, factor=tf, **nk)]))
         self.encoder = _Layers(enc)
         cm = config.middle_channel
         self.middle_block = _Middle([_Block(cm, cm, ce, None, a, circular=circ, **nk) for a in config.middle_block_attn_config])
@@ -593,7 +637,7 @@ class ADM(torch.nn.Module):
             # decoder_type 2 (ADMDecoderLayer2, :777-852): every block of the layer integrates the same skip again
             cmid = cb if config.decoder_type == 1 else cin
             dec.append(_Layer([_Block(cb, cmid, ce, circular=circ, **nk) for _ in range(nb - 1)] +
-                              [_Block(cb, cout, ce, "up", circular=circ, **nk)]))
+                              [_Block(cb, cout, ce, "up", circular=circ, factor=tf, **nk)]))
         self.decoder = _Layers(dec)
         self.input_layer = torch.nn.Conv2d(config.input_channels, mc, 3, padding="same")
         self.output_layer = torch.nn.Conv2d(mc, config.output_channels, 3, padding="same")
@@ -635,9 +679,19 @@ class ADM(torch.nn.Module):
             out = self.forward_unguarded(x, t, y)
         return out
 
+    def check_field_size(self, shape):
+        """H and W must divide by transition_scale_factor ** (number of transitions), else the decoder's resampled levels miss
+        the skips they join (the reference fails there, at the concat); raised before any launch."""
+        f, n = resample_factor(self.config.transition_scale_factor, "transition_scale_factor"), len(self.config.channel_expansion)
+        H, W = shape[-2], shape[-1]
+        if H % f ** n or W % f ** n:
+            raise ValueError(f"a {H}x{W} field does not divide by transition_scale_factor ** {n} = {f ** n} "
+                             f"({n} transitions by {f}): choose H and W multiples of {f ** n}")
+
     @ops.device_guard
     def forward_unguarded(self, x, t, y=None):
         ops.require_device(x, "x")
+        self.check_field_size(x.shape)
         te = self.embed_time(t.reshape(-1).to(x), self.embed_condition(y))
         shifts = self.time_shifts(te)
         return self.forward_with_shifts(x.contiguous(), shifts, row=None)
@@ -681,7 +735,8 @@ class ADM(torch.nn.Module):
             return self._packed
         pk = {}
         with torch.no_grad():
-            ups = {id(b.conv1) for b in blocks if b.sample == "up"} if getattr(self, "upsample_parity", True) else set()
+            ups = ({id(b.conv1) for b in blocks if b.sample == "up" and b.factor == 2} if getattr(self, "upsample_parity", True)
+                   else set())
             for m in convs:
                 pk[id(m)] = ops.pack_conv(m.weight.detach(), self.conv_precision, upsampled=id(m) in ups)
             if self.conv_precision == "fp16x3":
@@ -742,7 +797,9 @@ class ADM(torch.nn.Module):
         dev = x.device
         down, up = blk.sample == "down", blk.sample == "up"
         k1, k2 = blk.kinds                                     # 0 GroupNorm(1, C), 1 GroupRMSNorm(1, C)
-        Ho, Wo = (H // 2, W // 2) if down else ((2 * H, 2 * W) if up else (H, W))
+        f = blk.factor
+        Ho, Wo = (H // f, W // f) if down else ((f * H, f * W) if up else (H, W))
+        resample_f = (down or up) and f != 2       # any other factor: resampling kernels around plain convolutions
         mode = DS_LOAD_UPSAMPLE2 if up else DS_LOAD_PLAIN
         fused = self._fused()
         fuse1 = fused and (Ci + 63) // 64 <= self.fuse_max_cot            # per layer: see PUNetG.fuse_max_cot
@@ -767,7 +824,21 @@ class ADM(torch.nn.Module):
                 ops.gnorm1_stats_tiles(sa, k1, Ci * H * W, stats_b=sb, eps=1e-5, stats=stats)
             else:
                 ops.gnorm1_stats(x, k1, eps=1e-5, stats=stats, workspace=scratch)
-            if not up and self._norm_images_ok(blk.conv1, pk, Ci):
+            if resample_f:
+                # the norm pass pools by f itself ('down'), or the upsampling pass follows it at low resolution ('up'); the
+                # fused x2 loaders, parity kernels and image forms serve f = 2 only
+                if down:
+                    a = ops.gnorm1_apply_poolf(x, stats, blk.norm1.weight, blk.norm1.bias, k1, f, out=ws.take((B, Ci, Ho, Wo), dev))
+                else:
+                    a = ops.gnorm1_apply(x, stats, blk.norm1.weight, blk.norm1.bias, k1, out=ws.take((B, Ci, H, W), dev))
+                ia = self._normed_amax(blk, a)                                  # nearest upsampling keeps max |a|
+                if up:
+                    au = ops.upsample_f(a, f, out=ws.take((B, Ci, Ho, Wo), dev))
+                    ws.give(a)
+                    a = au
+                y = self._conv(blk.conv1, a, pk, tile_stats=ys, out=ws.take((B, blk.cout, Ho, Wo), dev), in_amax=ia)
+                ws.give(a)
+            elif not up and self._norm_images_ok(blk.conv1, pk, Ci):
                 # the standalone norm writes the convolution's pre-split fp16 images, staged there by LDS-DMA (see punetg._res)
                 img = ops.gnorm1_apply_images(x, stats, blk.norm1.weight, blk.norm1.bias, k1, pool=down,
                                               out=ws.take((ops.conv_images_floats(B, Ci, Hm, Wm),), dev))
@@ -793,7 +864,15 @@ class ADM(torch.nn.Module):
         # residual_block: convresidual(resample(x))                               (adm.py:345-349)
         r_up = False
         raw = self._raw_amax(x, xa) if pk[id(blk.convresidual)].kind == "fp16x3" else None       # pooling / upsampling keep max |x| a bound
-        if down and pk[id(blk.convresidual)].kind == "fp16x3":
+        if down and resample_f:
+            a = ops.avgpool_f(x, f, out=ws.take((B, Ci, Ho, Wo), dev))
+            r = self._conv(blk.convresidual, a, pk, out=ws.take((B, blk.cout, Ho, Wo), dev), in_amax=raw)
+            ws.give(a)
+        elif up and resample_f:                  # project at low resolution, then upsample the projection
+            a = self._conv(blk.convresidual, x, pk, out=ws.take((B, blk.cout, H, W), dev), in_amax=raw)
+            r = ops.upsample_f(a, f, out=ws.take((B, blk.cout, Ho, Wo), dev))
+            ws.give(a)
+        elif down and pk[id(blk.convresidual)].kind == "fp16x3":
             r = self._conv(blk.convresidual, x, pk, load_mode=DS_LOAD_AVGPOOL2, out=ws.take((B, blk.cout, Ho, Wo), dev), in_amax=raw)
         elif down:
             a = ops.gnorm1_apply(x, None, None, None, 2, pool=True, out=ws.take((B, Ci, Ho, Wo), dev))
@@ -880,6 +959,7 @@ class ADM(torch.nn.Module):
 
     def forward_with_shifts(self, x, shifts, row=None, out=None):
         """UNet body given the per-block FiLM rows (see PUNetG.forward_with_shifts)."""
+        self.check_field_size(x.shape)
         require_eval(self, self.config.dropout, self.config.cond_dropout)
         pk = self.packed_weights()
         ws = self._ws

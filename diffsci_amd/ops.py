@@ -577,6 +577,88 @@ def upsample3d(x, out=None):
     return out
 
 
+def _factor(factor):
+    import operator
+    try:
+        f = operator.index(factor)                   # ints and integer numpy scalars; floats and bools refused below
+    except TypeError:
+        f = None
+    if f is None or isinstance(factor, bool) or f < 1:
+        raise ValueError(f"resampling factor {factor!r} must be an integer >= 1")
+    return f
+
+
+def _film_args(film, B, C):
+    """(scale pointer, shift pointer, stride) of FiLM rows [1 or B, 2C] (embed_linear(te)), or (None, None, 0)."""
+    if film is None:
+        return None, None, 0
+    if film.dim() != 2 or film.shape[1] != 2 * C or film.shape[0] not in (1, B):
+        raise ValueError("film must be [1 or B, 2C]")
+    require_device(film, "film")
+    if not film.is_contiguous():
+        raise ValueError("film must be contiguous")
+    return film.data_ptr(), film.data_ptr() + 4 * C, (0 if film.shape[0] == 1 else 2 * C)
+
+
+def gnorm1_apply_poolf(x, stats, w, b, kind, factor, film=None, out=None):
+    """gnorm1_apply followed by AvgPool2d(factor) for any integer factor >= 1 (floor output size, as torch):
+    x [B, C, H, W] -> [B, C, H // f, W // f].  kind 2 pools the raw x."""
+    f = _factor(factor)
+    require_device(x, "x")
+    B, C, H, W = x.shape
+    if f > min(H, W):
+        raise ValueError(f"pooling factor {f} exceeds the field {H}x{W}")
+    if out is None:
+        out = torch.empty((B, C, H // f, W // f), dtype=torch.float32, device=x.device)
+    elif tuple(out.shape) != (B, C, H // f, W // f):
+        raise ValueError(f"out has shape {tuple(out.shape)}, expected {(B, C, H // f, W // f)}")
+    f1, f2, stride = _film_args(film, B, C)
+    N.check(N.lib().ds_gnorm1_apply_poolf(_p(out), _p(x), _p(stats), _p(w), _p(b), f1, f2, stride, B, C, H, W, int(kind), f,
+                                          _stream()), "ds_gnorm1_apply_poolf")
+    return out
+
+
+def avgpool_f(x, factor, out=None):
+    """AvgPool2d / AvgPool3d(kernel_size=factor) of a field [B, C, H, W] or a volume [B, C, D, H, W], any integer factor >= 1
+    (stride = factor, no padding, floor output size)."""
+    f = _factor(factor)
+    require_device(x, "x")
+    if x.dim() == 4:
+        return gnorm1_apply_poolf(x, None, None, None, 2, f, out=out)
+    if x.dim() != 5:
+        raise ValueError("avgpool_f takes [B, C, H, W] fields or [B, C, D, H, W] volumes")
+    B, C, Di, Hi, Wi = x.shape
+    if f > min(Di, Hi, Wi):
+        raise ValueError(f"pooling factor {f} exceeds the volume {Di}x{Hi}x{Wi}")
+    shape = (B, C, Di // f, Hi // f, Wi // f)
+    if out is None:
+        out = torch.empty(shape, dtype=torch.float32, device=x.device)
+    elif tuple(out.shape) != shape:
+        raise ValueError(f"out has shape {tuple(out.shape)}, expected {shape}")
+    N.check(N.lib().ds_avgpool3d_f(_p(out, "out"), _p(x, "x"), B * C, Di, Hi, Wi, f, _stream()), "ds_avgpool3d_f")
+    return out
+
+
+def upsample_f(x, factor, out=None):
+    """Upsample(scale_factor=factor, mode='nearest') of a field [B, C, H, W] or a volume [B, C, D, H, W], any integer
+    factor >= 1: out[..., y, x] = x[..., y // f, x // f] (and z // f on volumes)."""
+    f = _factor(factor)
+    require_device(x, "x")
+    if x.dim() not in (4, 5):
+        raise ValueError("upsample_f takes [B, C, H, W] fields or [B, C, D, H, W] volumes")
+    vol = x.dim() == 5
+    B, C = x.shape[:2]
+    Di, Hi, Wi = (x.shape[2:] if vol else (1,) + tuple(x.shape[2:]))
+    shape = (B, C) + ((f * Di,) if vol else ()) + (f * Hi, f * Wi)
+    if out is None:
+        out = torch.empty(shape, dtype=torch.float32, device=x.device)
+    elif tuple(out.shape) != shape:
+        raise ValueError(f"out has shape {tuple(out.shape)}, expected {shape}")
+    N.check(N.lib().ds_upsample_f(_p(out, "out"), _p(x, "x"), B * C, Di, Hi, Wi, f, 1 if vol else 0, _stream()),
+            "ds_upsample_f")
+    return out
+
+
 def gnorm1_stats(x, kind, eps=1e-5, stats=None, workspace=None):
     """Per-sample (mean, rstd) [kind 0] or (0, rms denominator) [kind 1] over (C, H, W)."""
     B, C = x.shape[0], x.shape[1]

@@ -400,6 +400,16 @@ int ds_slice_tables(float* table, const float* tile_stats, const float* w, const
 int ds_avgpool3d(float* out, const float* x, int planes, int Do, int Ho, int Wo, void* stream);
 int ds_upsample3d(float* out, const float* x, int planes, int Di, int Hi, int Wi, void* stream);
 
+/* Resampling by any integer factor f >= 1, the route of ADM blocks with image_sample_factor != 2 (AvgPool{2,3}d(kernel_size=f),
+ * Upsample(scale_factor=f, mode='nearest'), adm.py:361-383); factor 2 keeps the fused loaders above.
+ *   ds_avgpool3d_f: x [planes, Di, Hi, Wi] -> out [planes, Di/f, Hi/f, Wi/f] (floor: the remainder planes, rows and columns are
+ *     dropped); the f^3 voxels summed in (z, y, x) order, then / f^3.  f <= min(Di, Hi, Wi).
+ *   ds_upsample_f: out[p, z, y, x] = x[p, z/f, y/f, x/f]: volume = 1, x [planes, Di, Hi, Wi] -> out [planes, f*Di, f*Hi, f*Wi];
+ *     volume = 0 (fields), the depth axis is not resampled: out [planes, Di, f*Hi, f*Wi].  Bit-exact copies.
+ * Fields pool with ds_gnorm1_apply_poolf (kind 2 for the raw input). */
+int ds_avgpool3d_f(float* out, const float* x, int planes, int Di, int Hi, int Wi, int factor, void* stream);
+int ds_upsample_f(float* out, const float* x, int planes, int Di, int Hi, int Wi, int factor, int volume, void* stream);
+
 /* 1x1 convolution in the fp16x3 scheme of ds_conv2d_h3 (same epilogue terms, same domain and
  * in_amax / out_amax; amax_split > 0 (a multiple of 64): channels >= amax_split report to out_amax[B + b] instead of
  * out_amax[b] -- the attention in-projection keeps one exponent for q and k and one for v).  ADM's residual projection convresidual(resample(x)) (adm.py:345-349) with the
@@ -496,6 +506,13 @@ int ds_gnorm1_stats(float* stats, void* workspace, const float* x, int B, int C,
 int ds_gnorm1_apply(float* out, const float* x, const float* stats, const float* w, const float* b,
                     const float* film_scale, const float* film_shift, int film_stride,
                     int B, int C, int H, int W, int kind, int pool, void* stream);
+
+/* ds_gnorm1_apply with AvgPool2d(factor) for any factor >= 1 in place of the 2x2 pooling: x [B,C,H,W] -> out [B,C,H/f,W/f]
+ * (floor: the remainder rows and columns are dropped); each f x f window summed in row-major order, then / f^2.
+ * factor <= min(H, W).  Kinds and FiLM as ds_gnorm1_apply; kind 2 pools the raw x (the residual branch). */
+int ds_gnorm1_apply_poolf(float* out, const float* x, const float* stats, const float* w, const float* b,
+                          const float* film_scale, const float* film_shift, int film_stride,
+                          int B, int C, int H, int W, int kind, int factor, void* stream);
 
 /* out[b] = cat(a[b], b[b]) along channels (na, nb floats per sample): the decoder's skip concat,
  * adm.py:764-766. */

@@ -1,0 +1,85 @@
+"""Time the resampling kernels of the image_sample_factor != 2 route at config-3-like sizes (B = 8, 128-256 channels,
+64^2-256^2 fields, 3-D volumes), with the factor-2 kernels beside them, and one ADM-128 evaluation at 256^2 with
+transition_scale_factor 2 and 4.  Device events around 20 launches after a warm-up, three rounds; the median round is printed
+with the achieved HBM rate (bytes read once + bytes written, against the 8 TB/s peak)."""
+import os
+import sys
+sys.path.insert(0, os.getcwd())
+import torch
+from diffsci_amd import ops
+
+dev = torch.device("cuda:0")
+PEAK_GBS = 8000.0
+
+
+def timed(f, n=20):
+    f()
+    torch.cuda.synchronize()
+    rounds = []
+    for _ in range(3):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        for _ in range(n):
+            f()
+        e1.record()
+        torch.cuda.synchronize()
+        rounds.append(e0.elapsed_time(e1) / n * 1e3)
+    return sorted(rounds)[1]
+
+
+def report(name, f, nbytes):
+    us = timed(f)
+    gbs = nbytes / us / 1e3
+    print(f"{name:58s} {us:9.1f} us  {nbytes / 2**20:8.1f} MiB  {gbs:7.0f} GB/s  {100 * gbs / PEAK_GBS:5.1f}% of peak", flush=True)
+
+
+torch.manual_seed(0)
+# fields: upsampling (store-bound) and norm + SiLU + pooling (read-bound)
+for B, C, H in ((8, 128, 64), (8, 256, 64), (8, 128, 32)):
+    for f in (2, 3, 4):
+        x = torch.randn(B, C, H, H, device=dev)
+        out = torch.empty(B, C, f * H, f * H, device=dev)
+        report(f"upsample_f   [{B},{C},{H},{H}] x{f}", lambda: ops.upsample_f(x, f, out=out), 4 * (x.numel() + out.numel()))
+for B, C, H in ((8, 128, 256), (8, 256, 128)):
+    x = torch.randn(B, C, H, H, device=dev)
+    st = ops.gnorm1_stats(x, 0)
+    w, b = torch.randn(C, device=dev), torch.randn(C, device=dev)
+    o2 = torch.empty(B, C, H // 2, H // 2, device=dev)
+    report(f"gnorm1_apply pool=2 (f=2 route) [{B},{C},{H},{H}]",
+           lambda: ops.gnorm1_apply(x, st, w, b, 0, pool=True, out=o2), 4 * (x.numel() + o2.numel()))
+    for f in (2, 3, 4):
+        o = torch.empty(B, C, H // f, H // f, device=dev)
+        report(f"gnorm1_apply_poolf kind 0 [{B},{C},{H},{H}] /{f}",
+               lambda: ops.gnorm1_apply_poolf(x, st, w, b, 0, f, out=o), 4 * (x.numel() + o.numel()))
+        report(f"gnorm1_apply_poolf kind 2 [{B},{C},{H},{H}] /{f}",
+               lambda: ops.gnorm1_apply_poolf(x, None, None, None, 2, f, out=o), 4 * (x.numel() + o.numel()))
+    del x, o, o2
+# volumes
+for B, C, D in ((8, 128, 48),):
+    x = torch.randn(B, C, D, D, D, device=dev)
+    report(f"avgpool3d (f=2 route) [{B},{C},{D}^3]", lambda: ops.avgpool3d(x), 4 * x.numel() * 9 // 8)
+    for f in (2, 3, 4):
+        o = torch.empty(B, C, D // f, D // f, D // f, device=dev)
+        report(f"avgpool_f 3-D [{B},{C},{D}^3] /{f}", lambda: ops.avgpool_f(x, f, out=o), 4 * (x.numel() + o.numel()))
+    del x, o
+for B, C, D in ((8, 128, 16),):
+    x = torch.randn(B, C, D, D, D, device=dev)
+    report(f"upsample3d (f=2 route) [{B},{C},{D}^3]", lambda: ops.upsample3d(x), 4 * x.numel() * 9)
+    for f in (2, 3, 4):
+        o = torch.empty(B, C, f * D, f * D, f * D, device=dev)
+        report(f"upsample_f 3-D [{B},{C},{D}^3] x{f}", lambda: ops.upsample_f(x, f, out=o), 4 * (x.numel() + o.numel()))
+    del x, o
+torch.cuda.empty_cache()
+
+# one ADM-128 evaluation ([1, 2, 4] channel expansion, two transitions) at 256^2, B = 8: factor 2 against factor 4
+import diffsci_amd.models as M
+for f in (2, 4):
+    torch.manual_seed(0)
+    net = M.ADM(M.ADMConfig(input_channels=3, output_channels=3, model_channels=128, time_embed_dim=128, output_embed_dim=512,
+                            channel_expansion=[2, 4], transition_scale_factor=f)).to(dev)
+    x, t = torch.randn(8, 3, 256, 256, device=dev), torch.rand(8, device=dev)
+    with torch.no_grad():
+        us = timed(lambda: net(x, t), n=5)
+    print(f"ADM-128 [2, 4] eval, [8,3,256,256], transition_scale_factor={f}: {us / 1e3:8.2f} ms", flush=True)
+    del net
+    torch.cuda.empty_cache()

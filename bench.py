@@ -6,9 +6,13 @@ batch 64 per GPU (BASELINE.json configs[1]); synthetic random-init weights and G
     python bench.py --gpus N ...            # self-launching: starts N ranks through torch.distributed.run
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...   # or under a launcher
 
+    python bench.py --gpus 1 --steps 3 --warmup 1 --full     # + everything the headline does not need (below)
+
 One "step" = one full sampling run (50 Heun steps = 99 network evaluations) of one batch per
 rank, replayed from the captured hipGraph, followed (N>1) by the RCCL all-gather of the samples.
-Rank 0 prints ONE JSON line (schema: task contract + `roofline` + `cpu_baseline`).
+Rank 0 prints ONE JSON line: the task contract (headline, per-step spread, clock / power).  With --full the
+line also carries what takes runs of its own after the timed steps: `roofline` (dominant kernel),
+`roofline_hbm_class`, `other_precisions`, `other_configs` (configs 3 and 5) and `cpu_baseline`.
 """
 import argparse
 import json
@@ -106,13 +110,18 @@ def parse():
     ap.add_argument("--nsteps", type=int, default=50, help="Heun steps per sample")
     ap.add_argument("--size", type=int, default=128)
     ap.add_argument("--channels", type=int, default=64)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also measure what it does not need: the dominant kernel's roofline, the HBM-bound "
+                         "kernel classes, the other precisions, configs 3 and 5 and the CPU baseline (the --no-* options below "
+                         "leave parts of it out)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
     ap.add_argument("--force-dist", action="store_true",
                     help="go through the multi-rank code (RCCL process group, gather, barriers, all-reduce of the time) even with one rank "
                          "(also DIFFSCI_BENCH_FORCE_DIST=1): what one GPU can exercise of the N > 1 path")
     ap.add_argument("--no-graph", action="store_true")
-    ap.add_argument("--no-other-precisions", action="store_true", help="skip the bf16x6 / exact-fp32 legs of the line")
-    ap.add_argument("--no-other-configs", action="store_true", help="skip the config-3 (ADM-128) and config-5-share legs of the line")
+    ap.add_argument("--no-other-precisions", action="store_true", help="with --full: skip the bf16x6 / exact-fp32 legs of the line")
+    ap.add_argument("--no-other-configs", action="store_true",
+                    help="with --full: skip the config-3 (ADM-128) and config-5-share legs of the line")
     ap.add_argument("--fuse-max-cot", type=int, default=None, help="fuse norms only in layers with Cout/64 <= this")
     ap.add_argument("--no-up-parity", action="store_true", help="UpSampler convolutions through the generic gather loader")
     ap.add_argument("--no-direct-out", action="store_true", help="output layer on the MFMA kernel (Cout padded to 64)")
@@ -776,20 +785,21 @@ def main():
                                  "noise_draw_ms": [r[2] for r in per_rank],
                                  "gather_bytes_per_rank": int(B * args.size * args.size * 4)}
         print(f"[bench] {value:.3f} samples/s, {dt / args.steps * 1e3:.1f} ms per {B}-sample batch", file=sys.stderr, flush=True)
-        line["roofline"] = dominant_kernel_roofline(module, args, dev)
-        print(f"[bench] roofline {line['roofline']}", file=sys.stderr, flush=True)
-        line["roofline_hbm_class"] = hbm_class(module, args, dev)
-        print(f"[bench] hbm class {line['roofline_hbm_class']}", file=sys.stderr, flush=True)
-        if world == 1 and not args.no_other_precisions and args.precision == "fp16x3":
-            line["other_precisions"] = other_precisions(args, dev, noise[0])
-            print(f"[bench] other precisions {line['other_precisions']}", file=sys.stderr, flush=True)
-        if world == 1 and not args.no_other_configs and args.precision == "fp16x3":
-            del module
-            torch.cuda.empty_cache()
-            line["other_configs"] = other_configs(dev)
-            print(f"[bench] other configs {line['other_configs']}", file=sys.stderr, flush=True)
-        if not args.no_cpu_baseline and world == 1:
-            line["cpu_baseline"] = cpu_baseline(sd, cfg, args)
+        if args.full:           # after the timed steps and the dump, in runs of their own: nothing here feeds the headline
+            line["roofline"] = dominant_kernel_roofline(module, args, dev)
+            print(f"[bench] roofline {line['roofline']}", file=sys.stderr, flush=True)
+            line["roofline_hbm_class"] = hbm_class(module, args, dev)
+            print(f"[bench] hbm class {line['roofline_hbm_class']}", file=sys.stderr, flush=True)
+            if world == 1 and not args.no_other_precisions and args.precision == "fp16x3":
+                line["other_precisions"] = other_precisions(args, dev, noise[0])
+                print(f"[bench] other precisions {line['other_precisions']}", file=sys.stderr, flush=True)
+            if world == 1 and not args.no_other_configs and args.precision == "fp16x3":
+                del module
+                torch.cuda.empty_cache()
+                line["other_configs"] = other_configs(dev)
+                print(f"[bench] other configs {line['other_configs']}", file=sys.stderr, flush=True)
+            if not args.no_cpu_baseline and world == 1:
+                line["cpu_baseline"] = cpu_baseline(sd, cfg, args)
         print(json.dumps(line), flush=True)
     if dist is not None:
         dist.barrier()

@@ -380,6 +380,21 @@ def test_bench_dump_outputs_whole_and_sampled(tmp_path, monkeypatch):
         bench.parse()
 
 
+def test_bench_extra_legs_only_with_full(monkeypatch):
+    """A plain bench.py run does what its headline needs; the roofline, other precisions / configs and the CPU baseline are asked
+    for with --full, and the --no-* options still leave parts of that out."""
+    import importlib.util
+    spec = importlib.util.spec_from_file_location("bench_for_parse", os.path.join(ROOT, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    monkeypatch.setattr(bench.sys, "argv", ["bench.py", "--gpus", "1", "--steps", "3", "--warmup", "1"])
+    a = bench.parse()
+    assert a.full is False and (a.steps, a.warmup, a.gpus) == (3, 1, 1)
+    monkeypatch.setattr(bench.sys, "argv", ["bench.py", "--steps", "3", "--full", "--no-cpu-baseline"])
+    a = bench.parse()
+    assert a.full is True and a.no_cpu_baseline is True and a.no_other_configs is False
+
+
 def test_global_noise_skip_ahead_is_self_checked(monkeypatch):
     """The chunked per-rank draw leans on a detail of torch's CPU normal fill; the first use in a process checks it on a small
     case, and a torch that fails the check gets the full draw (same values) instead of silently different noise."""

@@ -7,6 +7,7 @@ mkdir -p gpurun_out
 for i in $(seq 1 $R); do
   for t in ${AB_TREES:-ab_r3 .}; do
     X=""; grep -q "no-other-configs" $t/bench.py && X="--no-other-configs"
+    grep -q '"--full"' $t/bench.py && X="$X --full"          # trees whose roofline moved behind --full
     ( cd $t && python bench.py --steps $S --warmup 2 --no-cpu-baseline --no-other-precisions $X 2>/dev/null | tail -1 | python -c "
 import sys, json
 d = json.loads(sys.stdin.read())

@@ -3,6 +3,9 @@
 // and parity kernels; these run as standalone passes between the norm and a plain convolution.
 //   ds_avgpool3d_f  volumes [planes, D, H, W] -> [planes, D/f, H/f, W/f] (floor), sum in torch's (z, y, x) order, / f^3.
 //                   (Fields pool inside ds_gnorm1_apply_poolf, kind 2 for the raw residual input.)
+//   ds_maxpool_f    fields and volumes [planes, (D,) H, W] -> floor(/ f), the max of each window in torch's (z, y, x) order with
+//                   its NaN rule (v > m || isnan(v), from -inf): the route of PUNetG's DownSampler with transition_scale_factor
+//                   != 2 (MaxPool{2,3}d(f), commonlayers.py:25-81).  Bit-identical to F.max_pool{2,3}d.
 //   ds_upsample_f   fields and volumes, out[.., z, y, x] = x[.., z/f, y/f, x/f].  A store-bound copy: each thread writes
 //                   16 bytes along W when W*f allows, reading its (at most 4) sources from the row just read by its
 //                   neighbours (L1 / L2 hits), so every source element leaves HBM once per output row.
@@ -67,6 +70,77 @@ __global__ __launch_bounds__(NT) void k_upsample_f(float* __restrict__ out, cons
   }
 }
 
+// max of v into m with torch's NaN rule (a NaN replaces anything; nothing replaces a NaN)
+__device__ __forceinline__ void max_into(float& m, float v) {
+  if (v > m || isnan(v)) m = v;
+}
+
+// VEC output floats per thread along W (4: Wo % 4 == 0 and out 16-byte aligned), consecutive lanes on consecutive outputs, so a
+// wave's window rows are one contiguous span of 64 * VEC * f floats.  F: the factor at compile time (2, 3, 4) or 0 (read from f):
+// with F known every row span of a thread (VEC * F floats) is loaded before any of it is compared, so a thread keeps all of them in
+// flight instead of one load per loop trip.  VLOAD: the row span is whole float4s (VEC * f and Wi multiples of 4, x 16-byte
+// aligned).  fd: the depth factor (f for volumes, 1 for fields).  32-bit indices: the host checks total.
+template <int F, int VEC, bool VLOAD>
+__global__ __launch_bounds__(NT) void k_maxpool_f(float* __restrict__ out, const float* __restrict__ x, int Di, int Hi, int Wi,
+                                                  unsigned Do, unsigned Ho, unsigned wq, int f_rt, int fd, unsigned total) {
+  const int f = F > 0 ? F : f_rt;
+  for (unsigned i = blockIdx.x * NT + threadIdx.x; i < total; i += gridDim.x * NT) {
+    const unsigned xq = i % wq, row = i / wq;
+    const unsigned yo = row % Ho, t = row / Ho;
+    const unsigned zo = t % Do, plane = t / Do;
+    const float* p = x + (((size_t)plane * Di + (size_t)zo * fd) * Hi + (size_t)yo * f) * Wi + (size_t)xq * VEC * f;
+    float m[VEC];
+#pragma unroll
+    for (int k = 0; k < VEC; ++k) m[k] = -INFINITY;
+    for (int dz = 0; dz < fd; ++dz) {
+      if constexpr (F > 0) {
+        constexpr int S = VEC * F;                       // floats per window row of this thread
+        float v[F][S];
+#pragma unroll
+        for (int dy = 0; dy < F; ++dy) {
+          const float* r = p + ((size_t)dz * Hi + dy) * Wi;
+          if constexpr (VLOAD) {
+#pragma unroll
+            for (int q = 0; q < S / 4; ++q) {
+              const float4 w = *reinterpret_cast<const float4*>(r + 4 * q);
+              v[dy][4 * q] = w.x; v[dy][4 * q + 1] = w.y; v[dy][4 * q + 2] = w.z; v[dy][4 * q + 3] = w.w;
+            }
+          } else {
+#pragma unroll
+            for (int q = 0; q < S; ++q) v[dy][q] = r[q];
+          }
+        }
+#pragma unroll
+        for (int dy = 0; dy < F; ++dy)                    // each window in (y, x) order, as torch
+#pragma unroll
+          for (int k = 0; k < VEC; ++k)
+#pragma unroll
+            for (int dx = 0; dx < F; ++dx) max_into(m[k], v[dy][k * F + dx]);
+      } else {
+        for (int dy = 0; dy < f; ++dy) {
+          const float* r = p + ((size_t)dz * Hi + dy) * Wi;
+#pragma unroll
+          for (int k = 0; k < VEC; ++k) {
+            const float* rk = r + k * f;
+            if constexpr (VLOAD) {                         // here f itself is a multiple of 4
+              for (int dx = 0; dx < f; dx += 4) {
+                const float4 w = *reinterpret_cast<const float4*>(rk + dx);
+                max_into(m[k], w.x); max_into(m[k], w.y); max_into(m[k], w.z); max_into(m[k], w.w);
+              }
+            } else {
+              for (int dx = 0; dx < f; ++dx) max_into(m[k], rk[dx]);
+            }
+          }
+        }
+      }
+    }
+    if (VEC == 4)
+      *reinterpret_cast<float4*>(out + (size_t)i * 4) = make_float4(m[0], m[1], m[2], m[3]);
+    else
+      out[i] = m[0];
+  }
+}
+
 }  // namespace
 
 extern "C" int ds_avgpool3d_f(float* out, const float* x, int planes, int Di, int Hi, int Wi, int factor, void* stream) {
@@ -115,5 +189,52 @@ extern "C" int ds_upsample_f(float* out, const float* x, int planes, int Di, int
     hipLaunchKernelGGL(k_upsample_f<1>, dim3((unsigned)g), dim3(NT), 0, s, out, x, Di, Hi, Wi, (unsigned)Do, (unsigned)Ho,
                        (unsigned)wq, (unsigned)factor, (unsigned)fd, (unsigned)total);
   DS_CHECK_LAUNCH("ds_upsample_f");
+  return DS_OK;
+}
+
+extern "C" int ds_maxpool_f(float* out, const float* x, int planes, int Di, int Hi, int Wi, int factor, int volume, void* stream) {
+  DS_REQUIRE(out && x, DS_ERR_NULL, "ds_maxpool_f: NULL pointer");
+  DS_REQUIRE(planes >= 0 && Di > 0 && Hi > 0 && Wi > 0, DS_ERR_SHAPE, "ds_maxpool_f: bad shape");
+  DS_REQUIRE(volume == 0 || volume == 1, DS_ERR_UNSUPPORTED, "ds_maxpool_f: volume %d", volume);
+  const int fd = volume ? factor : 1;
+  DS_REQUIRE(factor >= 1 && fd <= Di && factor <= Hi && factor <= Wi, DS_ERR_SHAPE,
+             "ds_maxpool_f: factor %d must be in [1, the smallest pooled side] (D=%d H=%d W=%d volume=%d)", factor, Di, Hi, Wi,
+             volume);
+  const int Do = Di / fd, Ho = Hi / factor, Wo = Wi / factor;
+  if (planes == 0) return DS_OK;
+  const bool vec = Wo % 4 == 0 && (reinterpret_cast<uintptr_t>(out) & 15u) == 0;
+  const int fc = factor >= 2 && factor <= 4 ? factor : 0;              // the factors with a compile-time kernel
+  // float4 row loads: a thread's row span (vec ? 4 : 1) * factor floats with a compile-time factor, each output's f floats otherwise
+  const int unit = fc ? (vec ? 4 : 1) * fc : factor;
+  const bool vload = unit % 4 == 0 && Wi % 4 == 0 && (reinterpret_cast<uintptr_t>(x) & 15u) == 0;
+  const size_t wq = vec ? Wo / 4 : Wo;
+  const size_t total = (size_t)planes * Do * Ho * wq;
+  DS_REQUIRE(total < (1ull << 32) - (size_t)MAX_BLOCKS * NT, DS_ERR_SHAPE, "ds_maxpool_f: output too large (%zu stores)", total);
+  size_t g = (total + NT - 1) / NT;
+  if (g > MAX_BLOCKS) g = MAX_BLOCKS;
+  hipStream_t s = ds::as_stream(stream);
+#define DS_MAXPOOL_LAUNCH(F, V, L)                                                                                              \
+  hipLaunchKernelGGL((k_maxpool_f<F, V, L>), dim3((unsigned)g), dim3(NT), 0, s, out, x, Di, Hi, Wi, (unsigned)Do, (unsigned)Ho, \
+                     (unsigned)wq, factor, fd, (unsigned)total)
+#define DS_MAXPOOL_VEC(F)                   \
+  do {                                      \
+    if (vec && vload)                       \
+      DS_MAXPOOL_LAUNCH(F, 4, true);        \
+    else if (vec)                           \
+      DS_MAXPOOL_LAUNCH(F, 4, false);       \
+    else if (vload)                         \
+      DS_MAXPOOL_LAUNCH(F, 1, true);        \
+    else                                    \
+      DS_MAXPOOL_LAUNCH(F, 1, false);       \
+  } while (0)
+  switch (fc) {
+    case 2: DS_MAXPOOL_VEC(2); break;
+    case 3: DS_MAXPOOL_VEC(3); break;
+    case 4: DS_MAXPOOL_VEC(4); break;
+    default: DS_MAXPOOL_VEC(0); break;
+  }
+#undef DS_MAXPOOL_VEC
+#undef DS_MAXPOOL_LAUNCH
+  DS_CHECK_LAUNCH("ds_maxpool_f");
   return DS_OK;
 }

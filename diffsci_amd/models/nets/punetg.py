@@ -7,7 +7,8 @@ give the reference's key names and default initialisers -- and are never called:
 operation of the forward pass is a launch into libdiffsci_hip.so:
 
   convin / convout / conv1+time-shift / conv2+residual   ds_conv2d (fp32 MFMA implicit GEMM)
-  DownSampler (max-pool -> conv), UpSampler (nearest -> conv) + skip add   ds_conv2d load modes
+  DownSampler (max-pool -> conv), UpSampler (nearest -> conv) + skip add   ds_conv2d load modes (transition_scale_factor 2),
+                                                            ds_maxpool_f / ds_upsample_f + plain conv (any other factor)
   GroupNorm(C,C)+SiLU, GroupRMSNorm(C,C)+SiLU              ds_inorm_silu
   GaussianFourierProjection, ResnetTimeBlock MLPs          ds_fourier_features, ds_linear
   TwoDimensionalAttention (nn.MultiheadAttention, 1 head)  ds_conv2d (1x1 projections) + ds_attention
@@ -22,7 +23,7 @@ import torch
 from ... import ops
 from ..._native import DS_LOAD_MAXPOOL2, DS_LOAD_UPSAMPLE2
 from . import precision
-from .punetg_config import PUNetGConfig
+from .punetg_config import PUNetGConfig, scale_factor
 
 
 class _AffineHolder(torch.nn.Module):
@@ -352,6 +353,10 @@ class PUNetG(torch.nn.Module):
         self.extra_residual = extra_residual
         self.capturable = extra_residual is None
         self.config = config
+        # transition_scale_factor: 2 pools / upsamples inside the Down / UpSamplers' convolution loaders (DS_LOAD_MAXPOOL2 /
+        # DS_LOAD_UPSAMPLE2, parity-packed upsampler weights); any other factor runs ds_maxpool_f / ds_upsample_f into a
+        # workspace buffer and the plain convolution after it
+        self.factor = scale_factor(config.transition_scale_factor)
         mc = config.model_channels
         mult = config.extended_channel_expansion
         self.time_projection = _Fourier(mc, config.time_projection_scale)
@@ -554,9 +559,23 @@ class PUNetG(torch.nn.Module):
             out = self.forward_unguarded(x, t, y)
         return out
 
+    def check_field_size(self, shape):
+        """With transition_scale_factor f != 2 every spatial side must divide by f ** (number of transitions), else a decoder
+        level misses the skip it joins (the reference fails there, at the addition); raised before any launch.  Factor 2 keeps
+        the checks of its loaders."""
+        f, n = self.factor, len(self.config.channel_expansion)
+        if f == 2 or n == 0:
+            return
+        sides = tuple(shape[2:])
+        if any(v % f ** n for v in sides):
+            what = "volume" if len(sides) == 3 else "field"
+            raise ValueError(f"a {'x'.join(map(str, sides))} {what} does not divide by transition_scale_factor ** {n} = {f ** n} "
+                             f"({n} transitions by {f}): choose sides that are multiples of {f ** n}")
+
     @ops.device_guard
     def forward_unguarded(self, x, t=None, y=None):
         ops.require_device(x, "x")
+        self.check_field_size(x.shape)
         B = x.shape[0]
         ye = self.embed_condition(y)
         if ye is not None and ye.dim() > 2:                       # a field of embeddings: per-pixel time shifts
@@ -733,14 +752,20 @@ class PUNetG(torch.nn.Module):
         for resnet_block, downsampler in zip(self.downward_blocks, self.downsamplers):
             x = self.resnet_block_forward(x, te, resnet_block)
             intermediate_outputs.append(x.clone())
-            x = self._conv(downsampler.conv, x, pk, load_mode=DS_LOAD_MAXPOOL2)
+            if self.factor == 2:
+                x = self._conv(downsampler.conv, x, pk, load_mode=DS_LOAD_MAXPOOL2)
+            else:
+                x = self._conv(downsampler.conv, ops.maxpool_f(x, self.factor), pk)
         return x, intermediate_outputs
 
     def decode(self, x, te, intermediate_outputs):
         """punetg.py:367-376 (pops the skips, like the reference)."""
         pk = self.packed_weights()
         for resnet_block, upsampler in zip(self.upward_blocks, self.upsamplers):
-            x = self._conv(upsampler.conv, x.contiguous(), pk, load_mode=DS_LOAD_UPSAMPLE2, res1=intermediate_outputs.pop())
+            if self.factor == 2:
+                x = self._conv(upsampler.conv, x.contiguous(), pk, load_mode=DS_LOAD_UPSAMPLE2, res1=intermediate_outputs.pop())
+            else:
+                x = self._conv(upsampler.conv, ops.upsample_f(x.contiguous(), self.factor), pk, res1=intermediate_outputs.pop())
             x = self.resnet_block_forward(x, te, resnet_block)
         return x
 
@@ -782,7 +807,8 @@ class PUNetG(torch.nn.Module):
             return self._packed
         pk = {}
         with torch.no_grad():
-            ups = {id(u.conv) for u in self.upsamplers} if getattr(self, "upsample_parity", True) else set()
+            # parity kernels exist for nearest x2 only: other factors upsample in a pass of their own
+            ups = {id(u.conv) for u in self.upsamplers} if getattr(self, "upsample_parity", True) and self.factor == 2 else set()
             for m in mods:
                 w = m.weight.detach()
                 if getattr(m, "mp", False):
@@ -997,11 +1023,13 @@ class PUNetG(torch.nn.Module):
         shared by the whole batch (sampling: sigma is a per-step constant), row=None means one row
         per sample (M == B).  Every activation travels with the tile statistics its producer left."""
         require_eval(self, self.config.dropout, self.config.cond_dropout, self.config.cond_drop)
+        self.check_field_size(x.shape)
         if self.dim == 3:
             return self._forward3d(x, shifts, row=row, out=out)
         pk = self.packed_weights()
         ws = self._ws
         cfg = self.config
+        f = self.factor
         B = x.shape[0]
         dev = x.device
         lazy_shifts = shifts if isinstance(shifts, _FieldShifts) else None
@@ -1095,10 +1123,17 @@ class PUNetG(torch.nn.Module):
                 if hs is not None:
                     ws.give(hs)                                                      # the skip is only added, never normalised
                 ds = self.downsamplers[lv].conv
-                Ho, Wo = h.shape[2] // 2, h.shape[3] // 2
+                Ho, Wo = h.shape[2] // f, h.shape[3] // f
                 hs = stats_for(first_block_after_level(lv), ds.out_channels, Ho, Wo)
-                h = self._conv(ds, h, pk, load_mode=DS_LOAD_MAXPOOL2, tile_stats=hs,
-                               out=ws.take((B, ds.out_channels, Ho, Wo), dev), in_amax=amax_of(h, ha))
+                if f == 2:
+                    h = self._conv(ds, h, pk, load_mode=DS_LOAD_MAXPOOL2, tile_stats=hs,
+                                   out=ws.take((B, ds.out_channels, Ho, Wo), dev), in_amax=amax_of(h, ha))
+                else:
+                    # max |maxpool(h)| <= max |h|: the producer's row of the unpooled h stays a valid exponent bound
+                    hp = ops.maxpool_f(h, f, out=ws.take((B, h.shape[1], Ho, Wo), dev))
+                    h = self._conv(ds, hp, pk, tile_stats=hs, out=ws.take((B, ds.out_channels, Ho, Wo), dev),
+                                   in_amax=amax_of(h, ha))
+                    ws.give(hp)
                 ha = None
             nattn, nafter = len(self.attn_resnet_block), len(self.after_block)
             for j, blk in enumerate(self.before_block):                               # punetg.py:378-387
@@ -1148,8 +1183,14 @@ class PUNetG(torch.nn.Module):
                 us = self.upsamplers[lv].conv
                 skip = skips.pop()
                 hs2 = stats_for(blocks[0] if len(blocks) else None, skip.shape[1], skip.shape[2], skip.shape[3])
-                h2 = self._conv(us, h, pk, load_mode=DS_LOAD_UPSAMPLE2, res1=skip, tile_stats=hs2,
-                                out=ws.take(skip.shape, dev), in_amax=amax_of(h, ha))
+                if f == 2:
+                    h2 = self._conv(us, h, pk, load_mode=DS_LOAD_UPSAMPLE2, res1=skip, tile_stats=hs2,
+                                    out=ws.take(skip.shape, dev), in_amax=amax_of(h, ha))
+                else:
+                    # a copy keeps max |h|: the producer's row bounds the upsampled tensor too
+                    hu = ops.upsample_f(h, f, out=ws.take((B, h.shape[1]) + tuple(skip.shape[2:]), dev))
+                    h2 = self._conv(us, hu, pk, res1=skip, tile_stats=hs2, out=ws.take(skip.shape, dev), in_amax=amax_of(h, ha))
+                    ws.give(hu)
                 give(h, hs)
                 ws.give(skip)
                 h, hs, ha = h2, hs2, None
@@ -1301,7 +1342,13 @@ class PUNetG(torch.nn.Module):
             skips.append(h)
             if hs is not None:
                 ws.give(hs)                                                      # the skip is only added, never normalised
-            h, hs = conv(self.downsamplers[lv].conv, h, load_mode=DS_LOAD_MAXPOOL2, want_stats=True)
+            if self.factor == 2:
+                h, hs = conv(self.downsamplers[lv].conv, h, load_mode=DS_LOAD_MAXPOOL2, want_stats=True)
+            else:                                                                # pooled volume, then the plain convolution
+                pooled = tuple(h.shape[:2]) + tuple(v // self.factor for v in h.shape[2:])
+                hp = ops.maxpool_f(h, self.factor, out=ws.take(pooled, dev))
+                h, hs = conv(self.downsamplers[lv].conv, hp, want_stats=True)
+                ws.give(hp)
         for blk in self.before_block:
             h2, hs2 = res(blk, h, hs)
             give(h, hs)
@@ -1329,7 +1376,12 @@ class PUNetG(torch.nn.Module):
         nup = len(self.upward_blocks)
         for lv, blocks in enumerate(self.upward_blocks):
             skip = skips.pop()
-            h2, hs2 = conv(self.upsamplers[lv].conv, h, load_mode=DS_LOAD_UPSAMPLE2, res1=skip, want_stats=True)
+            if self.factor == 2:
+                h2, hs2 = conv(self.upsamplers[lv].conv, h, load_mode=DS_LOAD_UPSAMPLE2, res1=skip, want_stats=True)
+            else:
+                hu = ops.upsample_f(h, self.factor, out=ws.take(tuple(h.shape[:2]) + tuple(skip.shape[2:]), dev))
+                h2, hs2 = conv(self.upsamplers[lv].conv, hu, res1=skip, want_stats=True)
+                ws.give(hu)
             give(h, hs)
             ws.give(skip)
             h, hs = h2, hs2
@@ -1459,6 +1511,7 @@ class PUNetGCond(PUNetG):
     @ops.device_guard
     def forward_unguarded(self, x, t, y=None):
         ops.require_device(x, "x")
+        self.check_field_size(x.shape)
         rest, self._ycat = self._split_condition(y)
         te = self.embed_time(t.reshape(-1).to(x), PUNetG.embed_condition(self, rest))
         shifts = self.time_shifts(te)
@@ -1472,6 +1525,7 @@ class PUNetGCond(PUNetG):
     def forward_with_shifts(self, x, shifts, row=None, out=None):
         if self._ycat is None:
             raise TypeError("PUNetGCond needs the condition dictionary y on every call (punetg.py:721-723)")
+        self.check_field_size(x.shape)
         xc = self._with_condition(x, self._ycat, self._ws)
         try:
             return super().forward_with_shifts(xc, shifts, row=row, out=out)

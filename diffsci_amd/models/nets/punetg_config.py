@@ -64,7 +64,7 @@ class PUNetGConfig(object):
             (self.convolution_type in ("default", "circular", "mp"), "convolution_type 'default', 'circular' or 'mp'"),
             (all(k in (1, 3, 5, 7) for k in (self.kernel_size, self.in_out_kernel_size)) and self.transition_kernel_size in (3, 5, 7),
              "kernel_size / in_out_kernel_size 1, 3, 5 or 7, transition_kernel_size 3, 5 or 7"),
-            (self.transition_scale_factor == 2, "transition_scale_factor=2"),
+            (scale_factor(self.transition_scale_factor) is not None, "an integer transition_scale_factor >= 1"),
             (not self.in_embedding or not self.bias,
              "in_embedding only with bias=False (the reference's ConvolutionalFourierProjection raises with bias=True, "
              "commonlayers.py:251-253)"),
@@ -72,3 +72,18 @@ class PUNetGConfig(object):
         ]
         bad = [msg for ok, msg in checks if not ok]
         return None if not bad else "diffsci_amd PUNetG supports: " + "; ".join(bad)
+
+
+def scale_factor(f):
+    """transition_scale_factor as an int >= 1 (ints, integer numpy scalars and integral floats, as ADMConfig takes them; MaxPool(f)
+    down, nearest Upsample(f) up), or None for anything else: a bool, a non-integer, zero or a negative number."""
+    import operator
+    if isinstance(f, bool):
+        return None
+    try:
+        f = operator.index(f)
+    except TypeError:
+        if not (isinstance(f, float) and f.is_integer()):
+            return None
+        f = int(f)
+    return f if f >= 1 else None

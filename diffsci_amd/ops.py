@@ -659,6 +659,28 @@ def upsample_f(x, factor, out=None):
     return out
 
 
+def maxpool_f(x, factor, out=None):
+    """MaxPool2d / MaxPool3d(kernel_size=factor) of a field [B, C, H, W] or a volume [B, C, D, H, W], any integer factor >= 1
+    (stride = factor, no padding, floor output size), bit-identical to torch (NaN windows give NaN)."""
+    f = _factor(factor)
+    if x.dim() not in (4, 5):
+        raise ValueError("maxpool_f takes [B, C, H, W] fields or [B, C, D, H, W] volumes")
+    require_device(x, "x")
+    vol = x.dim() == 5
+    B, C = x.shape[:2]
+    sides = tuple(x.shape[2:])
+    if f > min(sides):
+        raise ValueError(f"pooling factor {f} exceeds the {'volume' if vol else 'field'} {'x'.join(map(str, sides))}")
+    Di, Hi, Wi = sides if vol else (1,) + sides
+    shape = (B, C) + tuple(v // f for v in sides)
+    if out is None:
+        out = torch.empty(shape, dtype=torch.float32, device=x.device)
+    elif tuple(out.shape) != shape:
+        raise ValueError(f"out has shape {tuple(out.shape)}, expected {shape}")
+    N.check(N.lib().ds_maxpool_f(_p(out, "out"), _p(x, "x"), B * C, Di, Hi, Wi, f, 1 if vol else 0, _stream()), "ds_maxpool_f")
+    return out
+
+
 def gnorm1_stats(x, kind, eps=1e-5, stats=None, workspace=None):
     """Per-sample (mean, rstd) [kind 0] or (0, rms denominator) [kind 1] over (C, H, W)."""
     B, C = x.shape[0], x.shape[1]

@@ -410,6 +410,14 @@ int ds_upsample3d(float* out, const float* x, int planes, int Di, int Hi, int Wi
 int ds_avgpool3d_f(float* out, const float* x, int planes, int Di, int Hi, int Wi, int factor, void* stream);
 int ds_upsample_f(float* out, const float* x, int planes, int Di, int Hi, int Wi, int factor, int volume, void* stream);
 
+/* MaxPool2d / MaxPool3d(kernel_size=f) for any integer f >= 1 (stride f, no padding), the route of PUNetG's DownSampler with
+ * transition_scale_factor != 2 (commonlayers.py:25-81); factor 2 keeps the DS_LOAD_MAXPOOL2 loaders.  volume = 1: x [planes, Di,
+ * Hi, Wi] -> out [planes, Di/f, Hi/f, Wi/f]; volume = 0 (fields), the depth axis is not pooled: out [planes, Di, Hi/f, Wi/f].
+ * Floor: the remainder planes, rows and columns are dropped; f <= every pooled side.  Each window is scanned in (z, y, x) order
+ * from -inf with torch's rule m = (v > m || isnan(v)) ? v : m, so the result is bit-identical to F.max_pool{2,3}d: a window
+ * holding a NaN gives NaN, an all -inf window -inf. */
+int ds_maxpool_f(float* out, const float* x, int planes, int Di, int Hi, int Wi, int factor, int volume, void* stream);
+
 /* 1x1 convolution in the fp16x3 scheme of ds_conv2d_h3 (same epilogue terms, same domain and
  * in_amax / out_amax; amax_split > 0 (a multiple of 64): channels >= amax_split report to out_amax[B + b] instead of
  * out_amax[b] -- the attention in-projection keeps one exponent for q and k and one for v).  ADM's residual projection convresidual(resample(x)) (adm.py:345-349) with the

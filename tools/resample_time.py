@@ -1,7 +1,11 @@
 """Time the resampling kernels of the image_sample_factor != 2 route at config-3-like sizes (B = 8, 128-256 channels,
 64^2-256^2 fields, 3-D volumes), with the factor-2 kernels beside them, and one ADM-128 evaluation at 256^2 with
 transition_scale_factor 2 and 4.  Device events around 20 launches after a warm-up, three rounds; the median round is printed
-with the achieved HBM rate (bytes read once + bytes written, against the 8 TB/s peak)."""
+with the achieved HBM rate (bytes read once + bytes written, against the 8 TB/s peak).  The max-pool rows time PUNetG's
+transition_scale_factor != 2 route (ds_maxpool_f), next to eager PUNetG-64 evaluations with factors 2 and 4 in 2-D and 3-D.
+
+    python tools/resample_time.py            # everything
+    python tools/resample_time.py maxpool    # the max-pool rows and the PUNetG evaluations only"""
 import os
 import sys
 sys.path.insert(0, os.getcwd())
@@ -34,6 +38,44 @@ def report(name, f, nbytes):
 
 
 torch.manual_seed(0)
+ONLY_MAXPOOL = sys.argv[1:] == ["maxpool"]
+
+
+def maxpool_rows():
+    """ds_maxpool_f on shapes above the 256 MiB Infinity Cache, with torch's own kernel beside it."""
+    for shape in ((8, 128, 256, 256), (8, 256, 128, 128), (8, 128, 48, 48, 48)):
+        x = torch.randn(shape, device=dev)
+        tag = "x".join(map(str, shape))
+        for f in (2, 3, 4):
+            o = torch.empty(shape[:2] + tuple(v // f for v in shape[2:]), device=dev)
+            nbytes = 4 * (x.numel() + o.numel())
+            report(f"maxpool_f [{tag}] /{f}", lambda: ops.maxpool_f(x, f, out=o), nbytes)
+            pool = torch.nn.functional.max_pool3d if x.dim() == 5 else torch.nn.functional.max_pool2d
+            report(f"  torch max_pool [{tag}] /{f}", lambda: pool(x, f), nbytes)
+        del x, o
+    torch.cuda.empty_cache()
+
+
+def punetg_rows():
+    """One eager PUNetG-64 evaluation (channel_expansion [2, 4], as config 2): 2-D at B = 64, 128^2 and 3-D at B = 2, 64^3,
+    transition_scale_factor 2 against 4."""
+    import diffsci_amd.models as M
+    for dim, shape in ((2, (64, 1, 128, 128)), (3, (2, 1, 64, 64, 64))):
+        for f in (2, 4):
+            torch.manual_seed(0)
+            net = M.PUNetG(M.PUNetGConfig(dimension=dim, transition_scale_factor=f)).to(dev).eval()
+            x, t = torch.randn(shape, device=dev), torch.rand(shape[0], device=dev)
+            with torch.no_grad():
+                us = timed(lambda: net(x, t), n=5)
+            print(f"PUNetG-64 [2, 4] eval, [{','.join(map(str, shape))}], transition_scale_factor={f}: {us / 1e3:8.2f} ms", flush=True)
+            del net
+            torch.cuda.empty_cache()
+
+
+if ONLY_MAXPOOL:
+    maxpool_rows()
+    punetg_rows()
+    sys.exit(0)
 # fields: upsampling (store-bound) and norm + SiLU + pooling (read-bound)
 for B, C, H in ((8, 128, 64), (8, 256, 64), (8, 128, 32)):
     for f in (2, 3, 4):
@@ -83,3 +125,5 @@ for f in (2, 4):
     print(f"ADM-128 [2, 4] eval, [8,3,256,256], transition_scale_factor={f}: {us / 1e3:8.2f} ms", flush=True)
     del net
     torch.cuda.empty_cache()
+maxpool_rows()
+punetg_rows()

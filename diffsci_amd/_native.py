@@ -91,6 +91,7 @@ _PROTOS = {
     "ds_avgpool3d_f": (c_int, [_P, _P, c_int, c_int, c_int, c_int, c_int, _P]),
     "ds_upsample_f": (c_int, [_P, _P, c_int, c_int, c_int, c_int, c_int, c_int, _P]),
     "ds_maxpool_f": (c_int, [_P, _P, c_int, c_int, c_int, c_int, c_int, c_int, _P]),
+    "ds_cornerpool_f": (c_int, [_P, _P, _P, _P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, _P]),
     "ds_conv1x1_h3_packed_bytes": (c_size_t, [c_int, c_int]),
     "ds_conv1x1_h3_pack_weights": (c_int, [_P, _P, c_int, c_int, c_int, _P]),
     "ds_conv1x1_h3": (c_int, [_P, _P, _P, c_int, _P, _P, c_int, _P, _P, c_int, c_int, c_int, c_int, c_int, c_int, _P, _P, _P, c_int, _P]),

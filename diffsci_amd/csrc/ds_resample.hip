@@ -9,6 +9,10 @@
 //   ds_upsample_f   fields and volumes, out[.., z, y, x] = x[.., z/f, y/f, x/f].  A store-bound copy: each thread writes
 //                   16 bytes along W when W*f allows, reading its (at most 4) sources from the row just read by its
 //                   neighbours (L1 / L2 hits), so every source element leaves HBM once per output row.
+//   ds_cornerpool_f fields and volumes, out[b, c, o] = x[b or 0, c, o * f] (+ te[b or 0, c]): CornerPool{2,3}d(f) of a field-valued
+//                   conditional embedding with the time embedding added on the way (PUNetG's per-voxel time shifts), and the
+//                   per-sample max |out| for the fp16x3 1x1 convolution that reads it.  The same store-bound shape as
+//                   ds_upsample_f with the gather on the read side: for f >= 2 a thread's four sources are f floats apart.
 #include "ds_common.h"
 
 namespace {
@@ -141,7 +145,102 @@ __global__ __launch_bounds__(NT) void k_maxpool_f(float* __restrict__ out, const
   }
 }
 
+// Corner pooling with an optional per-(sample, channel) addend: out[b, c, z, y, x] = x[b or 0, c, z*fd, y*f, x*f] (+ te[b or 0, c]).
+// grid (blocks per sample, B): a block stays inside one sample, so its maximum |out| goes to that sample's amax slot with one
+// atomicMax per wave (the merge rule of k_absmax_rows: fmaxf drops NaNs, non-negative floats order like their bits).
+// VEC output floats per thread along W (4: Wo % 4 == 0 and out 16-byte aligned); VLOAD: f == 1 with x's rows whole aligned float4s.
+// xs / ts: the batch strides of x and te in floats (0: one sample shared by the batch).  `per` = C * Do * Ho * wq units per sample
+// fits 32 bits (the host checks).  ADD = false is a pure copy (-0.0 stays -0.0).
+template <int VEC, bool VLOAD, bool ADD>
+__global__ __launch_bounds__(NT) void k_cornerpool_f(float* __restrict__ out, const float* __restrict__ x, const float* __restrict__ te,
+                                                     unsigned* __restrict__ out_amax, size_t xs, size_t ts, int Di, int Hi, int Wi,
+                                                     unsigned Do, unsigned Ho, unsigned wq, unsigned f, unsigned fd, unsigned per) {
+  const unsigned b = blockIdx.y;
+  const float* xb = x + (size_t)b * xs;
+  const float* tb = ADD ? te + (size_t)b * ts : nullptr;
+  float* ob = out + (size_t)b * per * VEC;
+  float m = 0.f;
+  for (unsigned i = blockIdx.x * NT + threadIdx.x; i < per; i += gridDim.x * NT) {
+    const unsigned xq = i % wq, row = i / wq;
+    const unsigned yo = row % Ho, t = row / Ho;
+    const unsigned zo = t % Do, c = t / Do;
+    const float* src = xb + (((size_t)c * Di + (size_t)zo * fd) * Hi + (size_t)yo * f) * Wi + (size_t)xq * VEC * f;
+    const float a = ADD ? tb[c] : 0.f;
+    if (VEC == 4) {
+      float v[4];
+      if (VLOAD) {
+        const float4 w = *reinterpret_cast<const float4*>(src);
+        v[0] = w.x; v[1] = w.y; v[2] = w.z; v[3] = w.w;
+      } else {
+#pragma unroll
+        for (int k = 0; k < 4; ++k) v[k] = src[(size_t)k * f];
+      }
+      if (ADD) {
+#pragma unroll
+        for (int k = 0; k < 4; ++k) v[k] = v[k] + a;
+      }
+      *reinterpret_cast<float4*>(ob + (size_t)i * 4) = make_float4(v[0], v[1], v[2], v[3]);
+      m = fmaxf(m, fmaxf(fmaxf(__builtin_fabsf(v[0]), __builtin_fabsf(v[1])), fmaxf(__builtin_fabsf(v[2]), __builtin_fabsf(v[3]))));
+    } else {
+      float v = src[0];
+      if (ADD) v = v + a;
+      ob[i] = v;
+      m = fmaxf(m, __builtin_fabsf(v));
+    }
+  }
+  if (out_amax) {                                   // uniform: every lane of the block reaches the shuffles
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o, 64));
+    if ((threadIdx.x & 63) == 0) atomicMax(out_amax + b, __builtin_bit_cast(unsigned, m));
+  }
+}
+
 }  // namespace
+
+extern "C" int ds_cornerpool_f(float* out, const float* x, const float* te, unsigned* out_amax, int B, int C, int Di, int Hi, int Wi,
+                               int factor, int volume, int x_batch, int te_batch, void* stream) {
+  DS_REQUIRE(out && x, DS_ERR_NULL, "ds_cornerpool_f: NULL pointer");
+  DS_REQUIRE(B >= 0 && B < 65536 && C > 0 && Di > 0 && Hi > 0 && Wi > 0, DS_ERR_SHAPE, "ds_cornerpool_f: bad shape");
+  DS_REQUIRE(factor >= 1 && (volume == 0 || volume == 1), DS_ERR_UNSUPPORTED, "ds_cornerpool_f: factor %d volume %d", factor, volume);
+  DS_REQUIRE((x_batch == 1 || x_batch == B) && (!te || te_batch == 1 || te_batch == B), DS_ERR_SHAPE,
+             "ds_cornerpool_f: x_batch %d / te_batch %d must be 1 or B = %d", x_batch, te_batch, B);
+  const int fd = volume ? factor : 1;
+  DS_REQUIRE(Di % fd == 0 && Hi % factor == 0 && Wi % factor == 0, DS_ERR_SHAPE,
+             "ds_cornerpool_f: every pooled side must divide by the factor %d (D=%d H=%d W=%d volume=%d)", factor, Di, Hi, Wi, volume);
+  if (B == 0) return DS_OK;
+  const int Do = Di / fd, Ho = Hi / factor, Wo = Wi / factor;
+  const bool vec = Wo % 4 == 0 && (reinterpret_cast<uintptr_t>(out) & 15u) == 0;
+  const bool vload = vec && factor == 1 && (reinterpret_cast<uintptr_t>(x) & 15u) == 0;       // Wi == Wo: rows are whole float4s
+  const size_t wq = vec ? Wo / 4 : Wo;
+  const size_t per = (size_t)C * Do * Ho * wq;
+  DS_REQUIRE(per < (1ull << 32) - (size_t)MAX_BLOCKS * NT, DS_ERR_SHAPE, "ds_cornerpool_f: sample too large (%zu stores)", per);
+  size_t g = (per + NT - 1) / NT;
+  const size_t most = MAX_BLOCKS / (size_t)B > 0 ? MAX_BLOCKS / (size_t)B : 1;
+  if (g > most) g = most;
+  const size_t xs = x_batch == 1 ? 0 : (size_t)C * Di * Hi * Wi;
+  const size_t ts = te && te_batch != 1 ? (size_t)C : 0;
+  hipStream_t s = ds::as_stream(stream);
+#define DS_CORNERPOOL_LAUNCH(V, L, A)                                                                                          \
+  hipLaunchKernelGGL((k_cornerpool_f<V, L, A>), dim3((unsigned)g, (unsigned)B), dim3(NT), 0, s, out, x, te, out_amax, xs, ts, \
+                     Di, Hi, Wi, (unsigned)Do, (unsigned)Ho, (unsigned)wq, (unsigned)factor, (unsigned)fd, (unsigned)per)
+#define DS_CORNERPOOL_ADD(A)               \
+  do {                                     \
+    if (vload)                             \
+      DS_CORNERPOOL_LAUNCH(4, true, A);    \
+    else if (vec)                          \
+      DS_CORNERPOOL_LAUNCH(4, false, A);   \
+    else                                   \
+      DS_CORNERPOOL_LAUNCH(1, false, A);   \
+  } while (0)
+  if (te)
+    DS_CORNERPOOL_ADD(true);
+  else
+    DS_CORNERPOOL_ADD(false);
+#undef DS_CORNERPOOL_ADD
+#undef DS_CORNERPOOL_LAUNCH
+  DS_CHECK_LAUNCH("ds_cornerpool_f");
+  return DS_OK;
+}
 
 extern "C" int ds_avgpool3d_f(float* out, const float* x, int planes, int Di, int Hi, int Wi, int factor, void* stream) {
   DS_REQUIRE(out && x, DS_ERR_NULL, "ds_avgpool3d_f: NULL pointer");

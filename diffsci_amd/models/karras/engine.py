@@ -134,7 +134,7 @@ class ModuleSource:
         self.cfg = self.conditional and self.guidance != 1.0
         self.planned = bool(getattr(self.model, "forward_with_shifts", None)) and getattr(self.model, "capturable", True) and (
             like.dim() == 4 or (like.dim() == 5 and getattr(self.model, "dim", 2) == 3))
-        # A field-valued conditional embedding (punetg.py:405-407): the time shifts are per-pixel MLPs of te(sigma) + ye, so they are
+        # A field-valued conditional embedding (punetg.py:405-407; fields and volumes): the time shifts are per-pixel MLPs of te(sigma) + ye, so they are
         # computed inside every evaluation -- from the tabulated te row and a plan-owned copy of ye, out of the network's workspace
         # (PUNetG.field_shifts), which keeps the run capturable
         self.field = bool(self.planned and self.conditional and getattr(self.model, "condition_is_field", None)

@@ -11,6 +11,8 @@ operation of the forward pass is a launch into libdiffsci_hip.so:
                                                             ds_maxpool_f / ds_upsample_f + plain conv (any other factor)
   GroupNorm(C,C)+SiLU, GroupRMSNorm(C,C)+SiLU              ds_inorm_silu
   GaussianFourierProjection, ResnetTimeBlock MLPs          ds_fourier_features, ds_linear
+  ... with a field-valued conditional embedding            per-pixel / per-voxel MLPs as 1x1 convolutions at the block's resolution;
+                                                            on volumes ds_cornerpool_f forms te + ye there (CornerPool3d)
   TwoDimensionalAttention (nn.MultiheadAttention, 1 head)  ds_conv2d (1x1 projections) + ds_attention
   x + xa (punetg.py:385)                                    folded into the preceding conv epilogue
 """
@@ -301,15 +303,41 @@ class _FieldShifts:
     its three 1x1 convolutions at its own resolution (16x fewer pixels two levels down) from a pooled copy of te that the
     blocks of a level share.  Every buffer comes from the network's workspace, so the evaluation can sit inside a captured run."""
 
-    def __init__(self, te, ws, h3, owned=False):
+    def __init__(self, te, ws, h3, owned=False, rows=None, batch=None):
+        """2-D networks: te is the field te + ye [B, C, He, We].  Volumes: te is the embedded condition ye [1 or B, C, De, He, We]
+        alone, rows the time embedding [1 or B, C] (None: zeros) and batch the batch of x -- `level` adds the two while it pools
+        (ops.cornerpool_f), so their sum at the field's own resolution is never written."""
         self.te, self.ws, self.te_owned = te, ws, owned
-        self.am = _AmaxArena(ws, te.shape[0], te.device) if h3 else None
+        self.rows, self.batch = rows, te.shape[0] if batch is None else batch
+        self.am = _AmaxArena(ws, self.batch, te.device) if h3 else None
         self.levels = {}
 
-    def level(self, H, W):
-        """te at a block's resolution [B, C, H, W] and its amax row (fp16x3)."""
-        got = self.levels.get((H, W))
+    def _level_nd(self, dims):
+        """The volume form of `level`: one ds_cornerpool_f launch per resolution writes te + ye there and leaves its amax row.
+        The reference's rule (rescale_yt): the factor comes from the first side, every side must satisfy block * f == field."""
+        sp = tuple(self.te.shape[2:])
+        if len(dims) != len(sp):
+            raise ValueError(f"yt_dims {sp} and y_dims {dims} are not compatible")
+        if sp != dims and sp[0] <= dims[0]:
+            raise NotImplementedError("a conditional-embedding field coarser than a block's resolution (the reference's "
+                                      "upscaling branch passes the factor as torch.nn.Upsample's size and fails as well)")
+        f = sp[0] // dims[0]
+        if any(d * f != s for d, s in zip(dims, sp)):
+            raise ValueError(f"yt_dims {sp} and y_dims {dims} are not compatible")
+        a = self.am.row() if self.am is not None else None
+        t = ops.cornerpool_f(self.te, f, te=self.rows, out_amax=a,
+                             out=self.ws.take((self.batch, self.te.shape[1]) + dims, self.te.device))
+        return t, a, True
+
+    def level(self, *dims):
+        """te at a block's resolution -- level(H, W) -> [B, C, H, W], level(D, H, W) -> [B, C, D, H, W] -- and its amax row
+        (fp16x3)."""
+        dims = tuple(int(v) for v in dims)
+        got = self.levels.get(dims)
+        if got is None and (self.te.dim() != 4 or len(dims) != 2):
+            got = self.levels[dims] = self._level_nd(dims)
         if got is None:
+            H, W = dims
             B, C, h, w = self.te.shape
             if (h, w) == (H, W):
                 t, owned = self.te, False
@@ -576,19 +604,20 @@ class PUNetG(torch.nn.Module):
     def forward_unguarded(self, x, t=None, y=None):
         ops.require_device(x, "x")
         self.check_field_size(x.shape)
+        return self.forward_with_shifts(x.contiguous(), self._eager_shifts(x, t, self.embed_condition(y)), row=None)
+
+    def _eager_shifts(self, x, t, ye):
+        """The time shifts of one eager evaluation from the embedded condition ye (None, [1 or B, C] or a field)."""
         B = x.shape[0]
-        ye = self.embed_condition(y)
         if ye is not None and ye.dim() > 2:                       # a field of embeddings: per-pixel time shifts
-            shifts = self.field_shifts(None if t is None else self.embed_time(t.reshape(-1).to(x)), ye, B)
+            return self.field_shifts(None if t is None else self.embed_time(t.reshape(-1).to(x)), ye, B)
+        if t is None:                                              # punetg.py:398-399, 410: zeros (+ ye)
+            te = torch.zeros(B, self.config.model_channels, device=x.device)
+            if ye is not None:
+                te = te + ye
         else:
-            if t is None:                                          # punetg.py:398-399, 410: zeros (+ ye)
-                te = torch.zeros(B, self.config.model_channels, device=x.device)
-                if ye is not None:
-                    te = te + ye
-            else:
-                te = self.embed_time(t.reshape(-1).to(x), ye)
-            shifts = self.time_shifts(te)
-        return self.forward_with_shifts(x.contiguous(), shifts, row=None)
+            te = self.embed_time(t.reshape(-1).to(x), ye)
+        return self.time_shifts(te)
 
     # ------------------------------------------------------------------ conditioning
     def embed_condition(self, y):
@@ -596,13 +625,14 @@ class PUNetG(torch.nn.Module):
         if y is None:
             return None
         ye = y if self.conditional_embedding is None else self.conditional_embedding(y)
-        if ye.dim() == 2 + self.dim and self.dim == 2:            # punetg.py:405-407: a field [B or 1, C, H, W]
+        if ye.dim() == 2 + self.dim:                              # punetg.py:405-407: a field [B or 1, C, (D,) H, W]
             if ye.shape[1] != self.config.model_channels:
                 raise ValueError("a field-valued conditional embedding must have model_channels channels")
             ops.require_device(ye, "conditional embedding")
             return ye.detach().to(torch.float32).contiguous()         # inference only: the kernels carry no autograd graph
         if ye.dim() != 2:
-            raise NotImplementedError("field-valued conditional embeddings are implemented for 2-D networks ([B, C, H, W])")
+            raise ValueError(f"a conditional embedding is a vector [B or 1, C] or, on a dimension={self.dim} network, a field of "
+                             f"rank {2 + self.dim} ([B or 1, C, {'D, H, W' if self.dim == 3 else 'H, W'}]); got rank {ye.dim()}")
         return ye.to(torch.float32).contiguous()
 
     def condition_is_field(self, y):
@@ -614,12 +644,16 @@ class PUNetG(torch.nn.Module):
     def field_shifts(self, te, ye, B):
         """The time embedding as a field, te.reshape(B, C, 1, 1) + ye (punetg.py:405-410; te [1 or B, C] or None for zeros,
         ye [1 or B, C, He, We]), wrapped for the blocks to evaluate their per-pixel time MLPs from (`_FieldShifts`).  All
-        buffers are workspace buffers: forward_with_shifts gives them back."""
+        buffers are workspace buffers: forward_with_shifts gives them back.  On volumes (ye [1 or B, C, De, He, We]) the sum is
+        left to ds_cornerpool_f, which forms it at each block resolution while it pools: ye and te are handed over as they are
+        (the caller keeps them alive until forward_with_shifts returns)."""
         if ye.shape[0] not in (1, B):
             raise ValueError("conditional embedding batch must be 1 or match x")
         if te is not None and te.shape[0] not in (1, B):
             raise ValueError("time batch must be 1 or match x")
         ws = self._ws
+        if ye.dim() == 5:
+            return _FieldShifts(ye, ws, self.conv_precision == "fp16x3", rows=te, batch=B)
         field = ws.take((B,) + tuple(ye.shape[1:]), ye.device)
         if te is None:
             field.copy_(ye.expand(B, -1, -1, -1))
@@ -627,12 +661,18 @@ class PUNetG(torch.nn.Module):
             torch.add(te[:, :, None, None].expand(B, -1, 1, 1), ye, out=field)
         return _FieldShifts(field, ws, self.conv_precision == "fp16x3", owned=True)
 
-    def _field_shift(self, blk, fs, H, W):
+    def _field_shift(self, blk, fs, *dims):
         """ResnetTimeBlock of one block on the field at the block's resolution: the three linears as 1x1 convolutions on the
-        matrix cores, SiLU in between (commonlayers.py:537-546) -> [B, C_block, H, W] from the workspace (the caller gives it back)."""
+        matrix cores, SiLU in between (commonlayers.py:537-546) -> [B, C_block, H, W] from the workspace (the caller gives it back).
+        Volumes (dims = D, H, W): the same convolutions on the [B, C, D*H, W] view of the buffers -- a 1x1 convolution does not care
+        how the positions are laid out, and this view fills the kernel's 8 x 32 / 16 x 16 pixel tiles where [B, C, 1, D*H*W] would
+        use one row of each (measured: 140 of the 197 ms of a 64^3, B = 8 evaluation went to those launches)."""
         pk, ws = self._timeblock_convs(), fs.ws
-        te, a0 = fs.level(H, W)
+        te, a0 = fs.level(*dims)
         B, dev = te.shape[0], te.device
+        if len(dims) == 3:
+            te = te.view(B, te.shape[1], dims[0] * dims[1], dims[2])
+        H, W = te.shape[2:]
         n = blk.timeblock.net
         a1 = fs.am.row() if fs.am is not None else None
         a2 = fs.am.row() if fs.am is not None else None
@@ -645,7 +685,7 @@ class PUNetG(torch.nn.Module):
         out = ops.conv(h2, pk[id(n[4])], bias=n[4].bias, out=ws.take((B, n[4].out_features, H, W), dev), **self._amax_kw(in_amax=a2))
         ws.give(h)
         ws.give(h2)
-        return out
+        return out                                                   # volumes: [B, C_block, D*H, W], viewed by the caller
 
     def _timeblock_convs(self):
         lins = list(self._timeblock_linears())
@@ -1025,7 +1065,11 @@ class PUNetG(torch.nn.Module):
         require_eval(self, self.config.dropout, self.config.cond_dropout, self.config.cond_drop)
         self.check_field_size(x.shape)
         if self.dim == 3:
-            return self._forward3d(x, shifts, row=row, out=out)
+            try:
+                return self._forward3d(x, shifts, row=row, out=out)
+            finally:
+                if isinstance(shifts, _FieldShifts):
+                    shifts.release()
         pk = self.packed_weights()
         ws = self._ws
         cfg = self.config
@@ -1228,7 +1272,9 @@ class PUNetG(torch.nn.Module):
         ws = self._ws
         cfg = self.config
         B, dev = x.shape[0], x.device
-        it = iter(range(len(shifts)))
+        # a field of time shifts (_FieldShifts): every block evaluates its own per-voxel shift and adds it as conv1's residual
+        lazy_shifts = shifts if isinstance(shifts, _FieldShifts) else None
+        it = iter(range(len(shifts))) if lazy_shifts is None else None
         k1, k2 = self.norm_kinds
 
         def sh():
@@ -1248,7 +1294,9 @@ class PUNetG(torch.nn.Module):
         # norm1 inside the volume -> slice copy, the intermediate slice-major with norm2 in conv2's loader -- 20 instead of
         # 52 bytes per element of norm / copy traffic per block.  Without statistics (after the thin input layer or the
         # attention) the block runs the standalone norms and leaves statistics for its successor.
-        fold = self._fused() and self.extra_residual is None and k1 != 3 and k2 != 3 and cfg.kernel_size == 3
+        # (not with a field of shifts: resblock3d_fused adds one shift per channel, so those blocks run the standalone norms)
+        fold = (self._fused() and self.extra_residual is None and k1 != 3 and k2 != 3 and cfg.kernel_size == 3
+                and lazy_shifts is None)
 
         def stats_buf(shape):
             Bc, C, D, H, W = shape
@@ -1296,7 +1344,12 @@ class PUNetG(torch.nn.Module):
                 ws.give(tab)
                 return y, os_
             a = ops.inorm_silu(h, w1, b1, kind=k1, eps=1e-5, out=ws.take(h.shape, dev))
-            y, _ = conv(blk.conv1, a, shift=sh(), normalised=windowed)
+            if lazy_shifts is not None:
+                yt = self._field_shift(blk, lazy_shifts, *h.shape[2:])
+                y, _ = conv(blk.conv1, a, res1=yt.view((B, blk.conv1.out_channels) + tuple(h.shape[2:])), normalised=windowed)
+                ws.give(yt)
+            else:
+                y, _ = conv(blk.conv1, a, shift=sh(), normalised=windowed)
             ops.inorm_silu(y, w2, b2, kind=k2, eps=1e-5, out=a)
             if self.extra_residual is None:
                 _, os_ = conv(blk.conv2, a, res1=h, res2=res2, dst=y, want_stats=want_stats, normalised=windowed)
@@ -1513,8 +1566,7 @@ class PUNetGCond(PUNetG):
         ops.require_device(x, "x")
         self.check_field_size(x.shape)
         rest, self._ycat = self._split_condition(y)
-        te = self.embed_time(t.reshape(-1).to(x), PUNetG.embed_condition(self, rest))
-        shifts = self.time_shifts(te)
+        shifts = self._eager_shifts(x, t, PUNetG.embed_condition(self, rest))
         return self.forward_with_shifts(x.contiguous(), shifts, row=None)
 
     def embed_condition(self, y):

@@ -681,6 +681,38 @@ def maxpool_f(x, factor, out=None):
     return out
 
 
+def cornerpool_f(x, factor, te=None, out=None, out_amax=None):
+    """CornerPool2d / CornerPool3d(factor) of a field [Bx, C, H, W] or a volume [Bx, C, D, H, W] (the top-left corner of every
+    window), plus a per-(sample, channel) addend: out[b, c, o] = x[b or 0, c, o * f] (+ te[b or 0, c]), bit-identical to
+    x[..., ::f, ::f(, ::f)] + te[:, :, None, ...].  Any integer factor >= 1; every side must divide by it.  x and te [1 or B, C]
+    broadcast over the batch B (that of `out` when given, else the larger of the two).  out_amax: zeroed int32 [B] slots that
+    receive the per-sample max |out| (float bits, merged as absmax_rows does).  Shapes are checked before anything is launched."""
+    f = _factor(factor)
+    if not isinstance(x, torch.Tensor) or x.dim() not in (4, 5):
+        raise ValueError("cornerpool_f takes [B, C, H, W] fields or [B, C, D, H, W] volumes")
+    vol = x.dim() == 5
+    Bx, C = x.shape[:2]
+    sides = tuple(x.shape[2:])
+    if any(v % f for v in sides):
+        raise ValueError(f"every side of the {'volume' if vol else 'field'} {'x'.join(map(str, sides))} must divide by the "
+                         f"factor {f}")
+    if te is not None and (te.dim() != 2 or te.shape[1] != C):
+        raise ValueError(f"te must be [1 or B, {C}]; got {tuple(te.shape)}")
+    B = out.shape[0] if out is not None else max(Bx, 1 if te is None else te.shape[0])
+    if Bx not in (1, B) or (te is not None and te.shape[0] not in (1, B)):
+        raise ValueError(f"x {tuple(x.shape)} and te {None if te is None else tuple(te.shape)} must have batch 1 or {B}")
+    shape = (B, C) + tuple(v // f for v in sides)
+    if out is not None and tuple(out.shape) != shape:
+        raise ValueError(f"out has shape {tuple(out.shape)}, expected {shape}")
+    require_device(x, "x")
+    if out is None:
+        out = torch.empty(shape, dtype=torch.float32, device=x.device)
+    Di, Hi, Wi = sides if vol else (1,) + sides
+    N.check(N.lib().ds_cornerpool_f(_p(out, "out"), _p(x, "x"), _p(te, "te"), _pi(out_amax, B, "out_amax"), B, C, Di, Hi, Wi, f,
+                                    1 if vol else 0, Bx, 1 if te is None else te.shape[0], _stream()), "ds_cornerpool_f")
+    return out
+
+
 def gnorm1_stats(x, kind, eps=1e-5, stats=None, workspace=None):
     """Per-sample (mean, rstd) [kind 0] or (0, rms denominator) [kind 1] over (C, H, W)."""
     B, C = x.shape[0], x.shape[1]

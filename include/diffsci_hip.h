@@ -418,6 +418,16 @@ int ds_upsample_f(float* out, const float* x, int planes, int Di, int Hi, int Wi
  * holding a NaN gives NaN, an all -inf window -inf. */
 int ds_maxpool_f(float* out, const float* x, int planes, int Di, int Hi, int Wi, int factor, int volume, void* stream);
 
+/* CornerPool{2,3}d(f) (commonlayers.py:1035-1098: the top-left corner of every f-window) of a field-valued conditional embedding,
+ * with the time embedding added on the way: out[b, c, z, y, x] = x[b or 0, c, z*f, y*f, x*f] (+ te[b or 0, c]) -- the field te + ye
+ * of punetg.py:405-410 at a block's resolution in one pass.  x [x_batch, C, Di, Hi, Wi] -> out [B, C, Di/f, Hi/f, Wi/f] (volume =
+ * 0, fields: the depth axis is not pooled, out [B, C, Di, Hi/f, Wi/f]); x_batch and te_batch are 1 (shared by the batch) or B; te
+ * [te_batch, C] or NULL (a pure copy).  Any integer f >= 1; every pooled side must divide by f.  One fp32 addition per element,
+ * so the result is bit-identical to x[..., ::f, ::f] + te[:, :, None, None].  out_amax: NULL, or B zeroed slots that receive the
+ * per-sample max |out| as float bits (the format and merge rule of ds_absmax_rows). */
+int ds_cornerpool_f(float* out, const float* x, const float* te, unsigned* out_amax, int B, int C, int Di, int Hi, int Wi,
+                    int factor, int volume, int x_batch, int te_batch, void* stream);
+
 /* 1x1 convolution in the fp16x3 scheme of ds_conv2d_h3 (same epilogue terms, same domain and
  * in_amax / out_amax; amax_split > 0 (a multiple of 64): channels >= amax_split report to out_amax[B + b] instead of
  * out_amax[b] -- the attention in-projection keeps one exponent for q and k and one for v).  ADM's residual projection convresidual(resample(x)) (adm.py:345-349) with the

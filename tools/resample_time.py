@@ -5,7 +5,10 @@ with the achieved HBM rate (bytes read once + bytes written, against the 8 TB/s 
 transition_scale_factor != 2 route (ds_maxpool_f), next to eager PUNetG-64 evaluations with factors 2 and 4 in 2-D and 3-D.
 
     python tools/resample_time.py            # everything
-    python tools/resample_time.py maxpool    # the max-pool rows and the PUNetG evaluations only"""
+    python tools/resample_time.py maxpool    # the max-pool rows and the PUNetG evaluations only
+    python tools/resample_time.py field-eval # the PUNetG-64 64^3 evaluations alone (for a rocprofv3 kernel trace of the split)
+    python tools/resample_time.py cornerpool # ds_cornerpool_f next to ds_upsample_f / ds_maxpool_f at the same output sizes, and one
+                                             # PUNetG-64 evaluation at 64^3, B = 8 with a field against a vector embedding"""
 import os
 import sys
 sys.path.insert(0, os.getcwd())
@@ -72,6 +75,55 @@ def punetg_rows():
             torch.cuda.empty_cache()
 
 
+def cornerpool_rows():
+    """ds_cornerpool_f (te + ye at a block's resolution, with the amax row) counted as 8 bytes per output element -- 4 read, 4
+    written; for f >= 2 the reads use 1/f of every cache line along W -- next to ds_upsample_f and ds_maxpool_f writing the same
+    output, each counted by the bytes it reads once plus the bytes it writes."""
+    for out_shape in ((8, 64, 64, 64, 64), (8, 128, 32, 32, 32), (8, 128, 256, 256)):
+        B, C = out_shape[:2]
+        o = torch.empty(out_shape, device=dev)
+        te = torch.randn(B, C, device=dev)
+        amax = torch.zeros(B, dtype=torch.int32, device=dev)
+        tag = "x".join(map(str, out_shape))
+        for f in (1, 2, 3, 4):
+            x = torch.randn((1, C) + tuple(v * f for v in out_shape[2:]), device=dev)       # the sampler's shared field
+            report(f"cornerpool_f -> [{tag}] /{f} (+te, amax, shared x)", lambda: ops.cornerpool_f(x, f, te=te, out=o, out_amax=amax),
+                   8 * o.numel())
+            del x
+            if f > 1 and all(v % f == 0 for v in out_shape[2:]):
+                xu = torch.randn(out_shape[:2] + tuple(v // f for v in out_shape[2:]), device=dev)
+                report(f"  upsample_f -> [{tag}] x{f}", lambda: ops.upsample_f(xu, f, out=o), 4 * (xu.numel() + o.numel()))
+                del xu
+            if f > 1 and f * f * (f if len(out_shape) == 5 else 1) * o.numel() * 4 <= 8 << 30:
+                xm = torch.randn(out_shape[:2] + tuple(v * f for v in out_shape[2:]), device=dev)
+                report(f"  maxpool_f  -> [{tag}] /{f}", lambda: ops.maxpool_f(xm, f, out=o), 4 * (xm.numel() + o.numel()))
+                del xm
+        del o
+    torch.cuda.empty_cache()
+
+
+def punetg_field_rows():
+    """One eager PUNetG-64 evaluation (channel_expansion [2, 4]) at 64^3, B = 8: no condition, a vector embedding, a field
+    embedding (the per-voxel time MLPs, and the standalone norms in place of resblock3d_fused)."""
+    import diffsci_amd.models as M
+    torch.manual_seed(0)
+    net = M.PUNetG(M.PUNetGConfig(dimension=3), conditional_embedding=torch.nn.Identity()).to(dev).eval()
+    x, t = torch.randn(8, 1, 64, 64, 64, device=dev), torch.rand(8, device=dev)
+    conds = (("unconditional", None), ("vector embedding", torch.randn(8, 64, device=dev)),
+             ("field embedding 64^3", torch.randn(1, 64, 64, 64, 64, device=dev)))
+    for name, y in conds:
+        with torch.no_grad():
+            us = timed(lambda: net(x, t, y), n=5)
+        print(f"PUNetG-64 [2, 4] eval, [8,1,64,64,64], {name}: {us / 1e3:8.2f} ms", flush=True)
+
+
+if sys.argv[1:] == ["cornerpool"]:
+    cornerpool_rows()
+    punetg_field_rows()
+    sys.exit(0)
+if sys.argv[1:] == ["field-eval"]:
+    punetg_field_rows()
+    sys.exit(0)
 if ONLY_MAXPOOL:
     maxpool_rows()
     punetg_rows()
@@ -127,3 +179,5 @@ for f in (2, 4):
     torch.cuda.empty_cache()
 maxpool_rows()
 punetg_rows()
+cornerpool_rows()
+punetg_field_rows()

@@ -268,43 +268,61 @@ __global__ __launch_bounds__(256) void k_to_slices_act(float* S, const float* __
 // k_from_slices_stats: the copy back also leaves the shifted partial sums (K, S, Q, n) of what it stores, one entry per
 // workgroup, in ds_conv_epilogue.h's tile-statistics format: stats[(b*C + c)*(D*gx) + z*gx + blockIdx.x] -- the next
 // block's first norm needs no pass of its own over the volume.
+// The shift K is the mean of the workgroup's first (up to) 256 values, and the lanes' partial sums of S are added up in fp64 and
+// rounded once when stored: S then carries half an ulp of a SMALL number.  (With K = the first value alone and an fp32 tree, |S|
+// reached 1e3 per workgroup of 1024 values and the volume's sum was off by 1e-3 at 32768 voxels per channel -- ten times the 1e-4
+// the 2-D tile statistics are held to; tools/volume_check.py.)
 __global__ __launch_bounds__(256) void k_from_slices_stats(float* y, const float* __restrict__ S, const float* __restrict__ r1,
                                                           const float* __restrict__ r2, float* __restrict__ stats, int C,
                                                           int D, size_t HW, int pad) {
-  __shared__ float sk;
-  __shared__ float red[3][4];
+  __shared__ float kred[4], qred[4];
+  __shared__ double red[4];
   const int z = blockIdx.y % D;
   const int b = blockIdx.y / D;
   const int c = blockIdx.z;
   const float* src = S + (((size_t)b * (D + 2 * pad) + z + pad) * C + c) * HW;
   const size_t o = (((size_t)b * C + c) * D + z) * HW;
   const size_t first = (size_t)blockIdx.x * 256;
-  if (threadIdx.x == 0) {
-    float v = first < HW ? src[first] : 0.f;
-    if (first < HW && r1) v = v + r1[o + first];
-    if (first < HW && r2) v = v + r2[o + first];
-    sk = v;
+  const size_t i0 = first + threadIdx.x;
+  const size_t stride = (size_t)gridDim.x * 256;
+  const bool has = i0 < HW;
+  float v0 = 0.f;
+  if (has) {
+    v0 = src[i0];
+    if (r1) v0 = v0 + r1[o + i0];
+    if (r2) v0 = v0 + r2[o + i0];
   }
+  float ks = v0;
+  for (int k = 32; k > 0; k >>= 1) ks += __shfl_xor(ks, k, 64);
+  if ((threadIdx.x & 63) == 0) kred[threadIdx.x >> 6] = ks;
   __syncthreads();
-  const float K = sk;
-  float s1 = 0.f, s2 = 0.f, n = 0.f;
-  for (size_t i = first + threadIdx.x; i < HW; i += (size_t)gridDim.x * 256) {
+  const size_t kcount = first < HW ? (HW - first < 256 ? HW - first : 256) : 0;
+  const float K = kcount ? ((kred[0] + kred[1]) + (kred[2] + kred[3])) / (float)kcount : 0.f;
+  float t1 = 0.f, t2 = 0.f;                          // a lane's own few values (four up to 256 x 256 planes) in fp32, as before
+  if (has) {
+    y[o + i0] = v0;                                   // stored behind the barrier: in front of it the barrier would wait for the store
+    const float d = v0 - K;
+    t1 = d; t2 = d * d;
+  }
+  for (size_t i = i0 + stride; i < HW; i += stride) {
     float v = src[i];
     if (r1) v = v + r1[o + i];
     if (r2) v = v + r2[o + i];
     y[o + i] = v;
     const float d = v - K;
-    s1 += d; s2 += d * d; n += 1.f;
+    t1 += d; t2 += d * d;
   }
-  for (int k = 32; k > 0; k >>= 1) { s1 += __shfl_xor(s1, k, 64); s2 += __shfl_xor(s2, k, 64); n += __shfl_xor(n, k, 64); }
-  if ((threadIdx.x & 63) == 0) { red[0][threadIdx.x >> 6] = s1; red[1][threadIdx.x >> 6] = s2; red[2][threadIdx.x >> 6] = n; }
+  double s1 = t1;
+  for (int k = 32; k > 0; k >>= 1) { s1 += __shfl_xor(s1, k, 64); t2 += __shfl_xor(t2, k, 64); }
+  if ((threadIdx.x & 63) == 0) { red[threadIdx.x >> 6] = s1; qred[threadIdx.x >> 6] = t2; }
   __syncthreads();
   if (threadIdx.x == 0) {
-    const float S1 = (red[0][0] + red[0][1]) + (red[0][2] + red[0][3]);
-    const float S2 = (red[1][0] + red[1][1]) + (red[1][2] + red[1][3]);
-    const float Nn = (red[2][0] + red[2][1]) + (red[2][2] + red[2][3]);
+    const double S1 = (red[0] + red[1]) + (red[2] + red[3]);
+    const float S2 = (qred[0] + qred[1]) + (qred[2] + qred[3]);
+    float Nn = 0.f;                                   // the values this workgroup visited: whole rows of 256 but the last
+    for (size_t f = first; f < HW; f += stride) Nn += (float)(HW - f < 256 ? HW - f : 256);
     reinterpret_cast<float4*>(stats)[((size_t)b * C + c) * ((size_t)D * gridDim.x) + (size_t)z * gridDim.x + blockIdx.x] =
-        make_float4(K, S1, S2, Nn);
+        make_float4(K, (float)S1, S2, Nn);
   }
 }
 

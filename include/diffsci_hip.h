@@ -377,6 +377,8 @@ int ds_slices_to_volume(float* y, const float* slices, const float* res1, const 
  *     without a pass of its own.
  *   ds_slices_to_volume_stats: ds_slices_to_volume that also leaves the shifted partial sums (K, S, Q, n) of the stored values,
  *     stats [B, C, ds_volume_stat_tiles(D, HW), 4], for ds_inorm_table (count = D*HW) -- the NEXT block's first norm.
+ *     K is the mean of an entry's first (up to) 256 values and the lanes' partial sums of S are added up in fp64 and rounded once: a
+ *     channel's sum over 32768 voxels of order-one values is good to 1e-4 absolute.
  *   ds_slice_tables: for a volume that stays slice-major between the two convolutions of a block: the tile statistics of the
  *     last depth-tap launch (ds_conv2d_h3's tile_stats over the 2-D batch B*(D+2) - 2, sample j = slice j + 1) -> one
  *     (M, A, C) row per (slice, channel), table [B*(D+2), ceil16(C), 4]; pad slices get zero rows, so the consumer's fused

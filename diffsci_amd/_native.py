@@ -119,6 +119,11 @@ _PROTOS = {
     "ds_batchnorm_eval": (c_int, [_P, _P, _P, _P, _P, _P, c_float, c_float, c_int, c_int, c_int, c_int, c_size_t, _P]),
     "ds_lerp_stack": (c_int, [_P, _P, _P, c_int, c_size_t, _P]),
     "ds_add": (c_int, [_P, _P, _P, c_size_t, _P]),
+    "ds_token_layernorm": (c_int, [_P, _P, _P, _P, _P, _P, c_int, c_int, c_int, c_int, c_float, _P, _P]),
+    "ds_token_gate": (c_int, [_P, _P, _P, _P, c_int, c_int, c_int, c_int, _P]),
+    "ds_silu_amax": (c_int, [_P, _P, c_int, c_size_t, _P, _P]),
+    "ds_patch_embed": (c_int, [_P, _P, _P, _P, c_int, c_int, c_int, c_int, c_int, c_int, _P]),
+    "ds_patch_unembed": (c_int, [_P, _P, _P, _P, c_int, c_int, c_int, c_int, c_int, c_int, _P]),
     "ds_graph_begin_capture": (c_int, [_P]),
     "ds_graph_end_capture": (c_int, [_P, POINTER(_P), POINTER(c_int)]),
     "ds_graph_launch": (c_int, [_P, _P]),

@@ -1319,6 +1319,130 @@ def fourier_features(t, W, add=None, out=None):
     return out
 
 
+# ---------------------------------------------------------------- token-wise layers of the DiffusionTransformer (ds_tokens.hip)
+def _mod_rows(table, E, B, row, what):
+    """A modulation table [rows, n*E] (chunks of E along its rows) for B samples -> (first float of sample 0's row, stride in
+    floats between samples).  row=None: the table has 1 (shared) or B rows; row=r: row r serves the whole batch."""
+    require_device(table, what)
+    if table.dim() != 2 or table.shape[1] % E or not table.is_contiguous():
+        raise ValueError(f"{what} must be a contiguous [rows, n*{E}] table; got {tuple(table.shape)}")
+    width = table.shape[1]
+    if row is not None:
+        row = int(row)
+        if not 0 <= row < table.shape[0]:
+            raise ValueError(f"{what}: row {row} outside the table's {table.shape[0]} rows")
+        return row * width, 0
+    if table.shape[0] not in (1, B):
+        raise ValueError(f"{what} must have 1 or {B} rows; got {table.shape[0]}")
+    return 0, (0 if table.shape[0] == 1 else width)
+
+
+def token_layernorm(x, w, b, mod=None, shift_chunk=0, scale_chunk=1, row=None, eps=1e-5, out=None, out_amax=None):
+    """LayerNorm(E) of every token of x [B, E, L] (channel-major), then adaLN modulation
+    out = LN(x) * (1 + scale) + shift, with shift / scale the chunks `shift_chunk` / `scale_chunk` (of E floats) of the rows of
+    `mod` [rows, n*E]: 1 or B rows, or the single row `row` for the whole batch (the captured sampler's table).  mod=None: the
+    plain LayerNorm.  out_amax: int32 [B] slots (zeroed) that receive the per-sample max |out| for an fp16x3 consumer."""
+    require_device(x, "x")
+    if x.dim() != 3:
+        raise ValueError("token_layernorm: x must be [B, E, L]")
+    B, E, L = x.shape
+    for t, what in ((w, "weight"), (b, "bias")):
+        if t is not None and t.numel() != E:
+            raise ValueError(f"token_layernorm: {what} must have E={E} entries")
+    if out is None:
+        out = torch.empty_like(x)
+    elif tuple(out.shape) != (B, E, L) or out.data_ptr() == x.data_ptr():
+        raise ValueError("token_layernorm: out must be a [B, E, L] tensor other than x")
+    psc = psh = None
+    stride = 0
+    if mod is not None:
+        first, stride = _mod_rows(mod, E, B, row, "mod")
+        n = mod.shape[1] // E
+        if not (0 <= shift_chunk < n and 0 <= scale_chunk < n):
+            raise ValueError("token_layernorm: chunk outside the table")
+        psh = mod.data_ptr() + 4 * (first + shift_chunk * E)
+        psc = mod.data_ptr() + 4 * (first + scale_chunk * E)
+    N.check(N.lib().ds_token_layernorm(_p(out, "out"), _p(x, "x"), _p(w, "weight"), _p(b, "bias"), psc, psh, stride, B, E, L, float(eps),
+                                       _pi(out_amax, B, "out_amax"), _stream()), "ds_token_layernorm")
+    return out
+
+
+def token_gate(x, y, mod, chunk=0, row=None, out=None):
+    """x + gate * y on [B, E, L] with gate the chunk `chunk` of the rows of mod (as token_layernorm); out may be x (in place)."""
+    require_device(x, "x")
+    if x.dim() != 3 or tuple(y.shape) != tuple(x.shape):
+        raise ValueError("token_gate: x and y must be [B, E, L]")
+    B, E, L = x.shape
+    first, stride = _mod_rows(mod, E, B, row, "mod")
+    if not 0 <= chunk < mod.shape[1] // E:
+        raise ValueError("token_gate: chunk outside the table")
+    if out is None:
+        out = torch.empty_like(x)
+    elif tuple(out.shape) != (B, E, L) or out.data_ptr() == y.data_ptr():
+        raise ValueError("token_gate: out must be [B, E, L] and may alias x only")
+    N.check(N.lib().ds_token_gate(_p(out, "out"), _p(x, "x"), _p(y, "y"), mod.data_ptr() + 4 * (first + chunk * E), stride, B, E, L,
+                                  _stream()), "ds_token_gate")
+    return out
+
+
+def silu_amax(x, out=None, out_amax=None):
+    """SiLU(x) for x [B, ...] (out may be x), the per-sample max |out| merged into out_amax (int32 [B]) when given."""
+    require_device(x, "x")
+    B = x.shape[0]
+    if out is None:
+        out = torch.empty_like(x)
+    elif tuple(out.shape) != tuple(x.shape):
+        raise ValueError("silu_amax: out must have x's shape")
+    N.check(N.lib().ds_silu_amax(_p(out, "out"), _p(x, "x"), B, x.numel() // max(B, 1), _pi(out_amax, B, "out_amax"), _stream()),
+            "ds_silu_amax")
+    return out
+
+
+def _patch_dims(shape, patch, what):
+    if len(shape) != 4:
+        raise ValueError(f"{what}: the image must be [B, C, H, W]")
+    B, C, H, W = shape
+    patch = int(patch)
+    if patch < 1 or H % patch or W % patch:
+        raise ValueError(f"{what}: a {H}x{W} image does not divide into {patch}x{patch} patches")
+    return B, C, H, W, patch, (H // patch) * (W // patch)
+
+
+def patch_embed(x, w, bias, patch, out=None):
+    """x [B, C, H, W] -> tokens [B, E, L]: Linear(C*patch^2, E) of the patches flattened in (c p1 p2) order, token h*(W/patch) + w."""
+    require_device(x, "x")
+    B, C, H, W, patch, L = _patch_dims(x.shape, patch, "patch_embed")
+    E = w.shape[0]
+    if tuple(w.shape) != (E, C * patch * patch) or (bias is not None and bias.numel() != E):
+        raise ValueError(f"patch_embed: weight must be [E, {C * patch * patch}] and bias [E]; got {tuple(w.shape)}")
+    if out is None:
+        out = torch.empty((B, E, L), dtype=torch.float32, device=x.device)
+    elif tuple(out.shape) != (B, E, L):
+        raise ValueError(f"patch_embed: out must be {(B, E, L)}")
+    N.check(N.lib().ds_patch_embed(_p(out, "out"), _p(x, "x"), _p(w, "weight"), _p(bias, "bias"), B, C, H, W, patch, E, _stream()),
+            "ds_patch_embed")
+    return out
+
+
+def patch_unembed(x, w, bias, patch, shape, out=None):
+    """tokens x [B, E, L] -> image `shape` = (B, C, H, W): Linear(E, C*patch^2), then the inverse patch map."""
+    require_device(x, "x")
+    B, C, H, W, patch, L = _patch_dims(tuple(shape), patch, "patch_unembed")
+    if x.dim() != 3 or x.shape[0] != B or x.shape[2] != L:
+        raise ValueError(f"patch_unembed: x must be [{B}, E, {L}]; got {tuple(x.shape)}")
+    E = x.shape[1]
+    K = C * patch * patch
+    if tuple(w.shape) != (K, E) or (bias is not None and bias.numel() != K):
+        raise ValueError(f"patch_unembed: weight must be [{K}, {E}] and bias [{K}]; got {tuple(w.shape)}")
+    if out is None:
+        out = torch.empty((B, C, H, W), dtype=torch.float32, device=x.device)
+    elif tuple(out.shape) != (B, C, H, W):
+        raise ValueError(f"patch_unembed: out must be {(B, C, H, W)}")
+    N.check(N.lib().ds_patch_unembed(_p(out, "out"), _p(x, "x"), _p(w, "weight"), _p(bias, "bias"), B, C, H, W, patch, E, _stream()),
+            "ds_patch_unembed")
+    return out
+
+
 def fourier_channels(x, W, out=None):
     """ConvolutionalFourierProjection: x [B, C, *spatial], W [C, D] -> [B, 2D, *spatial] = cat[sin, cos](x . 2*pi*W)."""
     require_device(x, "x")

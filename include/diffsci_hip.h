@@ -571,6 +571,43 @@ int ds_lerp_stack(float* out, const float* x1, const float* x2, int n, size_t nu
 int ds_add(float* out, const float* a, const float* b, size_t n, void* stream);
 
 /* ------------------------------------------------------------------------------------
+ * DiffusionTransformer score-network layers (difftransformer.py): the token-wise part.
+ * Tensors are channel-major [B, E, L] with the L tokens contiguous (the layout of the 1x1
+ * convolutions and of the attention), fp32.  Modulation rows are slices of the
+ * [rows, 6E] table chunk6(adaln_modulation(te)) (difftransformer.py:163-168): the pointer
+ * of sample 0's slice plus the stride in floats between samples, 0 = one row for the batch.
+ * ---------------------------------------------------------------------------------- */
+
+/* torch.nn.LayerNorm(E) over the embedding axis of every token, then adaln_modulate (difftransformer.py:23-28,148-149,171,174):
+ *   out[b,e,l] = ((x[b,e,l] - mean[b,l]) * rstd[b,l] * w[e] + b[e]) * (1 + mod_scale[b*mod_stride + e]) + mod_shift[b*mod_stride + e]
+ * mean and the biased variance over e, rstd = 1/sqrt(var + eps).  The statistics are two passes over registers on values shifted
+ * by the token's first channel (never E[x^2] - mean^2).  w, b, mod_scale, mod_shift may each be NULL (1, 0, 0, 0).  out_amax
+ * (optional, int32 [B], zeroed or merged into): float bits of max |out[b]| for the fp16x3 launch that reads out.  E <= 1024.
+ * out may not alias x. */
+int ds_token_layernorm(float* out, const float* x, const float* w, const float* b, const float* mod_scale, const float* mod_shift,
+                       int mod_stride, int B, int E, int L, float eps, unsigned* out_amax, void* stream);
+
+/* The gated residual of a DiT block (difftransformer.py:169-174): out[b,e,l] = x[b,e,l] + gate[b*gate_stride + e] * y[b,e,l], a
+ * rounded product and a rounded sum.  out may alias x (not y). */
+int ds_token_gate(float* out, const float* x, const float* y, const float* gate, int gate_stride, int B, int E, int L, void* stream);
+
+/* out = SiLU(x) on [B, n_per_sample] with the per-sample max |out| merged into out_amax (optional, as above): the activation
+ * between the two linears of a DiT block's MLP (difftransformer.py:152-156), whose output feeds an fp16x3 launch.  out may alias x. */
+int ds_silu_amax(float* out, const float* x, int B, size_t n_per_sample, unsigned* out_amax, void* stream);
+
+/* Patcher.forward + embed (difftransformer.py:9-13,77-80,231-232): x [B, C, H, W] -> out [B, E, L], L = (H/patch) * (W/patch),
+ *   out[b,e,l] = bias[e] + sum_k w[e,k] * x[b, c, h*patch + p1, w*patch + p2],  k = (c*patch + p1)*patch + p2,  l = h*(W/patch) + w
+ * w [E, C*patch^2] (torch Linear layout), exact fp32: an fmaf chain in k order, then the bias.  H and W multiples of patch. */
+int ds_patch_embed(float* out, const float* x, const float* w, const float* bias, int B, int C, int H, int W, int patch, int E,
+                   void* stream);
+
+/* unembed + Patcher.inverse (difftransformer.py:16-20,86-94,234-235): x [B, E, L] -> y [B, C, H, W],
+ *   y[b, c, h*patch + p1, w*patch + p2] = bias[k] + sum_e w[k,e] * x[b,e,l]
+ * w [C*patch^2, E], exact fp32: four fmaf chains over quarters of the E axis, added in order, then the bias. */
+int ds_patch_unembed(float* y, const float* x, const float* w, const float* bias, int B, int C, int H, int W, int patch, int E,
+                     void* stream);
+
+/* ------------------------------------------------------------------------------------
  * hipGraph capture of a launch sequence (the whole N-step loop is captured once per
  * (network, nsteps, batch) and replayed).
  * ---------------------------------------------------------------------------------- */

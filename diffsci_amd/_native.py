@@ -109,6 +109,10 @@ _PROTOS = {
     "ds_fourier_channels": (c_int, [_P, _P, _P, c_int, c_int, c_int, c_size_t, _P]),
     "ds_gnorm1_workspace_bytes": (c_size_t, [c_int]),
     "ds_gnorm1_stats": (c_int, [_P, _P, _P, c_int, c_int, c_int, c_float, c_int, _P]),
+    "ds_groupnorm_stats": (c_int, [_P, _P, _P, c_int, c_int, c_int, c_int, c_float, _P]),
+    "ds_groupnorm_apply": (c_int, [_P, _P, _P, _P, _P, c_int, c_int, c_int, c_int, c_int, _P, _P]),
+    "ds_groupnorm_stats_tiles": (c_int, [_P, _P, c_int, c_int, c_int, c_int, c_longlong, c_float, _P]),
+    "ds_groupnorm_table": (c_int, [_P, _P, _P, _P, _P, c_int, c_int, c_int, c_int, c_longlong, c_float, _P]),
     "ds_gnorm1_apply": (c_int, [_P, _P, _P, _P, _P, _P, _P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, _P]),
     "ds_gnorm1_apply_poolf": (c_int, [_P, _P, _P, _P, _P, _P, _P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, _P]),
     "ds_concat2": (c_int, [_P, _P, _P, c_int, c_size_t, c_size_t, _P]),

@@ -331,6 +331,7 @@ __global__ void k_add_act(float* out, const float* __restrict__ a, const float* 
   if (add) v = v + add[(size_t)(add_rows == 1 ? 0 : m) * N + n];
   if (act == 1) v = silu(v);
   else if (act == 2) v = fmaxf(v, 0.f);
+  else if (act == 3) v = tanhf(v);
   out[i] = v;
 }
 
@@ -471,7 +472,7 @@ int ds_concat2(float* out, const float* a, const float* b, int B, size_t na, siz
 
 int ds_add_act(float* out, const float* a, const float* add, int add_rows, int M, int N, int act, void* stream) {
   DS_REQUIRE(out && a, DS_ERR_NULL, "ds_add_act: NULL pointer");
-  DS_REQUIRE(M >= 0 && N > 0 && act >= 0 && act <= 2, DS_ERR_SHAPE, "ds_add_act: bad arguments");
+  DS_REQUIRE(M >= 0 && N > 0 && act >= 0 && act <= 3, DS_ERR_SHAPE, "ds_add_act: bad arguments");
   DS_REQUIRE(add == nullptr || add_rows == 1 || add_rows == M, DS_ERR_SHAPE, "ds_add_act: add_rows=%d must be 1 or M=%d", add_rows, M);
   if (M == 0) return DS_OK;
   hipLaunchKernelGGL(k_add_act, dim3((M * N + 255) / 256), dim3(256), 0, ds::as_stream(stream), out, a, add, add_rows,

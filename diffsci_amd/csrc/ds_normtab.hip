@@ -18,30 +18,13 @@
 // inside the fp16x3 window whatever the norm's affine parameters, FiLM rows or eps-dominated variances do
 // (commonlayers.py:766-770: (x - mean)/sqrt(var + 1e-5) of a tensor of rms 1e-7 is 3e-5, not 1).  The value rides in the rows
 // the loader reads anyway: no extra load, no atomics.
-#include "ds_common.h"
+#include "ds_normtab_common.h"
 
 namespace {
 
-__device__ __forceinline__ double group_sum_d(double v, int width) {
-  for (int o = width >> 1; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-
-__device__ __forceinline__ void acc_tile(const float4 v, double& s, double& q) {
-  const double K = v.x, S = v.y, Q = v.z, n = v.w;
-  s += n * K + S;
-  q += Q + 2.0 * K * S + n * K * K;
-}
-
-// 2^-k for a bound U on the activation's argument: U * 2^k in [2^13, 2^14); |k| <= 80 keeps 2^-(wshift + k) a normal float for
-// every weight shift (|wshift| <= 40)
-__device__ __forceinline__ float inv_scale_of(float U) {
-  const unsigned bits = __builtin_bit_cast(unsigned, U);
-  const int e = (int)((bits >> 23) & 0xffu);
-  int k = (e == 0 || e == 255) ? 0 : 140 - e;
-  k = k > 80 ? 80 : (k < -80 ? -80 : k);
-  return __builtin_bit_cast(float, (unsigned)(127 - k) << 23);
-}
+using ds_nt::acc_tile;
+using ds_nt::group_sum_d;
+using ds_nt::inv_scale_of;
 
 // one workgroup per sample, 16 lanes per (b, c) plane, 64 planes at a time
 constexpr int ITT = 1024;

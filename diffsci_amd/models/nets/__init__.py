@@ -5,3 +5,7 @@ from .adm import (ADM, ADMBaseBlock, ADMConfig, ADMDecoder, ADMDecoderBlock, ADM
                   ADMMiddleBlock, ADMTimeEmbedding)
 from .embedder import PorosityEmbedder  # noqa: F401
 from .dit import DiffusionTransformer  # noqa: F401
+from .autoencoders import LDMAutoencoderKLWrapper  # noqa: F401
+from . import autoencoderldm2d, autoencoderldm3d  # noqa: F401
+# the reference star-exports both modules, the 3-D one last: these names are the volume classes
+from .autoencoderldm3d import AttnBlock, AutoencoderKL, Decoder, ResnetBlock, Upsample, ddconfig  # noqa: F401

@@ -749,6 +749,110 @@ def gnorm1_apply(x, stats, w, b, kind, pool=False, film=None, out=None):
     return out
 
 
+# ---------------------------------------------------------------- GroupNorm(G, C) with several channels per group (ds_groupnorm.hip)
+def _groupnorm_dims(x, G, what):
+    require_device(x, "x")
+    if x.dim() < 3:
+        raise ValueError(f"{what}: x must be [B, C, *spatial]")
+    B, C = x.shape[0], x.shape[1]
+    G = int(G)
+    if G < 1 or C % G:
+        raise ValueError(f"{what}: C={C} is not a multiple of num_groups={G}")
+    return B, C, G, x.numel() // max(B * C, 1)
+
+
+def _affine(w, b, C, what):
+    for t, name in ((w, "weight"), (b, "bias")):
+        if t is not None and t.numel() != C:
+            raise ValueError(f"{what}: norm {name} must have C={C} entries")
+
+
+def groupnorm_stats(x, G, eps=1e-6, stats=None, workspace=None):
+    """(mean, rstd) [B, G, 2] of GroupNorm(G, C) over x [B, C, *spatial] (biased variance, fp64 accumulation)."""
+    B, C, G, n = _groupnorm_dims(x, G, "groupnorm_stats")
+    if stats is None:
+        stats = torch.empty((B, G, 2), dtype=torch.float32, device=x.device)
+    elif tuple(stats.shape) != (B, G, 2):
+        raise ValueError(f"stats must be {(B, G, 2)}")
+    need = N.lib().ds_gnorm1_workspace_bytes(B * G)
+    if workspace is None:
+        workspace = torch.empty(need // 4, dtype=torch.float32, device=x.device)
+    elif workspace.numel() * 4 < need:
+        raise ValueError("groupnorm workspace too small")
+    N.check(N.lib().ds_groupnorm_stats(_p(stats, "stats"), _p(workspace, "workspace"), _p(x, "x"), B, C, G, n, float(eps), _stream()),
+            "ds_groupnorm_stats")
+    return stats
+
+
+def groupnorm_apply(x, stats, w, b, G, act=False, out=None, out_amax=None):
+    """(x - mean[b,g]) * rstd[b,g] * w[c] + b[c], then SiLU when act; x [B, C, *spatial], stats [B, G, 2].  out_amax: zeroed
+    int32 [B] slots that receive the per-sample max |out| (as conv2d's)."""
+    B, C, G, n = _groupnorm_dims(x, G, "groupnorm_apply")
+    if tuple(stats.shape) != (B, G, 2):
+        raise ValueError(f"stats must be {(B, G, 2)}; got {tuple(stats.shape)}")
+    _affine(w, b, C, "groupnorm_apply")
+    if out is None:
+        out = torch.empty_like(x)
+    elif tuple(out.shape) != tuple(x.shape):
+        raise ValueError("groupnorm_apply: out must have x's shape")
+    N.check(N.lib().ds_groupnorm_apply(_p(out, "out"), _p(x, "x"), _p(stats, "stats"), _p(w, "weight"), _p(b, "bias"), B, C, G, n,
+                                       1 if act else 0, _pi(out_amax, B, "out_amax"), _stream()), "ds_groupnorm_apply")
+    return out
+
+
+def groupnorm_stats_tiles(tile_stats, G, count, eps=1e-6, stats=None):
+    """groupnorm_stats [B, G, 2] from the tile statistics [B, C, ntiles, 4] of the tensor's producing convolution instead of
+    a pass over the tensor; count: positions per channel."""
+    require_device(tile_stats, "tile_stats")
+    B, C, nt, _ = tile_stats.shape
+    G = int(G)
+    if G < 1 or C % G:
+        raise ValueError(f"groupnorm_stats_tiles: C={C} is not a multiple of num_groups={G}")
+    if stats is None:
+        stats = torch.empty((B, G, 2), dtype=torch.float32, device=tile_stats.device)
+    elif tuple(stats.shape) != (B, G, 2):
+        raise ValueError(f"stats must be {(B, G, 2)}")
+    N.check(N.lib().ds_groupnorm_stats_tiles(_p(stats, "stats"), _p(tile_stats, "tile_stats"), B, C, G, nt, int(count), float(eps),
+                                             _stream()), "ds_groupnorm_stats_tiles")
+    return stats
+
+
+def groupnorm_table(w, b, G, count, tile_stats=None, stats=None, eps=1e-6, out=None):
+    """GroupNorm(G, C) + SiLU as the prenorm table [B, ceil16(C), 4] of the consuming 3x3 fp16x3 convolution (rows as
+    inorm_table), from the producer's tile_stats [B, C, ntiles, 4] or from plain stats [B, G, 2]; count: positions per channel."""
+    if (tile_stats is None) == (stats is None):
+        raise ValueError("groupnorm_table: give tile_stats or stats")
+    G = int(G)
+    if tile_stats is not None:
+        require_device(tile_stats, "tile_stats")
+        B, C, nt, _ = tile_stats.shape
+    else:
+        require_device(stats, "stats")
+        if w is None or stats.dim() != 3 or tuple(stats.shape[1:]) != (G, 2):
+            raise ValueError("groupnorm_table: stats must be [B, G, 2] and the weight gives the channel count")
+        B, C, nt = stats.shape[0], w.numel(), 0
+    if G < 1 or C % G:
+        raise ValueError(f"groupnorm_table: C={C} is not a multiple of num_groups={G}")
+    _affine(w, b, C, "groupnorm_table")
+    if out is None:
+        out = torch.empty((B, table_channels(C), 4), dtype=torch.float32, device=(tile_stats if stats is None else stats).device)
+    elif tuple(out.shape) != (B, table_channels(C), 4):
+        raise ValueError(f"table must be {(B, table_channels(C), 4)}")
+    N.check(N.lib().ds_groupnorm_table(_p(out, "table"), _p(tile_stats, "tile_stats"), _p(stats, "stats"), _p(w, "weight"), _p(b, "bias"),
+                                       B, C, G, nt, int(count), float(eps), _stream()), "ds_groupnorm_table")
+    return out
+
+
+def tanh(x, out=None):
+    """tanh(x), any shape."""
+    require_device(x, "x")
+    out = torch.empty_like(x) if out is None else out
+    if x.numel() >= 1 << 31:
+        raise ValueError("tanh: at most 2^31 - 1 elements")
+    N.check(N.lib().ds_add_act(_p(out, "out"), _p(x, "x"), None, 0, 1, x.numel(), 3, _stream()), "ds_add_act")
+    return out
+
+
 def concat2(a, b, out=None):
     """cat([a, b], dim=1) for [B, C, H, W] tensors."""
     B = a.shape[0]

@@ -515,6 +515,27 @@ size_t ds_gnorm1_workspace_bytes(int B);
 int ds_gnorm1_stats(float* stats, void* workspace, const float* x, int B, int C, int HW, float eps, int kind,
                     void* stream);
 
+/* GroupNorm(G, C) with C/G >= 1 channels per group (the LDM AutoencoderKL decoder: GroupNorm(32, C), eps 1e-6,
+ * autoencoderldm2d.py:17-21), on x [B, C, N] with the N positions of a channel contiguous (fields and volumes), g = c / (C/G).
+ * ds_groupnorm_stats: stats[b, g] = (mean, 1/sqrt(var_biased + eps)), fp64 accumulation in a fixed order; a group is one contiguous
+ *   run of (C/G)*N floats, so this is ds_gnorm1_stats on the [B*G] view; workspace: ds_gnorm1_workspace_bytes(B*G) bytes.
+ * ds_groupnorm_apply: out = (x - mean[b,g]) * rstd[b,g] * w[c] + b[c] (w, b optional), then SiLU when act = 1 (act = 0: none), in
+ *   one pass; 16-byte accesses when N % 4 == 0 and out, x are 16-byte aligned, a scalar path otherwise.  out_amax: optional [B]
+ *   slots as above (per-sample max |out|, merged by one maximum per workgroup).
+ * ds_groupnorm_stats_tiles: the pairs of ds_groupnorm_stats without a pass over x, recombined in fp64 from the tile statistics
+ *   [B, C, ntiles, 4] its producing convolution left (count = N, the positions per channel).
+ * ds_groupnorm_table: the consuming 3x3 convolution's prenorm table [B, ceil16(C), 4] = (M, A, C, 2^-k) as ds_inorm_table /
+ *   ds_gnorm1_table write it -- M = mean[b,g], A = rstd[b,g]*w[c], C = b[c], the sample's activation exponent from the bound
+ *   max_c |A_c| sqrt(n_g var_g) + |C_c|, zero rows past C -- from tile_stats (stats NULL) or from plain [B, G, 2] pairs
+ *   (tile_stats NULL, ntiles ignored).  G <= 1024. */
+int ds_groupnorm_stats(float* stats, void* workspace, const float* x, int B, int C, int G, int N, float eps, void* stream);
+int ds_groupnorm_apply(float* out, const float* x, const float* stats, const float* w, const float* b, int B, int C, int G, int N,
+                       int act, unsigned* out_amax, void* stream);
+int ds_groupnorm_stats_tiles(float* stats, const float* tile_stats, int B, int C, int G, int ntiles, long long count, float eps,
+                             void* stream);
+int ds_groupnorm_table(float* table, const float* tile_stats, const float* stats, const float* w, const float* b, int B, int C,
+                       int G, int ntiles, long long count, float eps, void* stream);
+
 /* One elementwise pass fusing the normalisation with what follows it in ADMBaseBlock (adm.py:306-343):
  *   kind 0: SiLU(n) or SiLU(n*scale[b,c] + shift[b,c]), n = (x-mean)*rstd*w[c]+b[c]     GroupNorm(1, C)
  *   kind 1: likewise with n = x/denom*w[c]+b[c]                                          GroupRMSNorm(1, C)
@@ -538,8 +559,8 @@ int ds_gnorm1_apply_poolf(float* out, const float* x, const float* stats, const 
  * adm.py:764-766. */
 int ds_concat2(float* out, const float* a, const float* b, int B, size_t na, size_t nb, void* stream);
 
-/* out[m,n] = act(a[m,n] + add[m or 0, n]); act as in ds_linear.  ADMTimeEmbedding's "te + ye" and
- * final SiLU (adm.py:1050-1052). */
+/* out[m,n] = act(a[m,n] + add[m or 0, n]); act as in ds_linear, and 3 = tanh (the LDM decoder's tanh_out,
+ * autoencoderldm2d.py:472-473).  ADMTimeEmbedding's "te + ye" and final SiLU (adm.py:1050-1052). */
 int ds_add_act(float* out, const float* a, const float* add, int add_rows, int M, int N, int act, void* stream);
 
 /* out[b, i] = x[b, i]*(1 - mask[i]) + y[b, i]*mask[i]: the known-region re-imposition of

@@ -535,8 +535,7 @@ int launch_attn3h(float* out, const float* qkv, void* workspace, int B, int head
     DS_CHECK_LAUNCH("ds_attention_h3 (images)");
   }
   dim3 g((L + 127) / 128, rows);
-  static const float thr = [] { const char* e = getenv("DS_ATTN_T"); return e ? (float)atof(e) : RESCALE_T; }();   // diagnostic knob
-  hipLaunchKernelGGL((k_attn3h<ET, IMG, MH>), g, dim3(NT), lds, s, out, qkv, kimg, vimg, L, heads, B, scale, thr, in_amax,
+  hipLaunchKernelGGL((k_attn3h<ET, IMG, MH>), g, dim3(NT), lds, s, out, qkv, kimg, vimg, L, heads, B, scale, RESCALE_T, in_amax,
                      out_amax);
   DS_CHECK_LAUNCH("ds_attention_h3");
   return DS_OK;

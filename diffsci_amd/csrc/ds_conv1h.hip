@@ -290,22 +290,19 @@ __global__ void k_pack1h(_Float16* packed, const float* __restrict__ w, int Cout
 }
 
 // Two channel tiles per workgroup where the output has an even number of them and the halved grid still fills the chip
-// (DS_CONV1_TWO_MIN workgroups, 256 = one per CU).  Measured on MI355X (tools/conv1h_time.py, batch 32): 512 -> 256 at 128^2
+// (TWO_MIN_WORKGROUPS, 256 = one per CU).  Measured on MI355X (tools/conv1h_time.py, batch 32): 512 -> 256 at 128^2
 // 626 -> 565 us, 768 -> 384 at 64^2 331 -> 292, 1024 -> 512 at 32^2 142 -> 118, 384 -> 128 at 256^2 1070 -> 962, the attention
 // in-projection 256 -> 768 at 32^2 (batch 64) 127.5 -> 114.  DS_CONV1_TWO=0 switches it off, =2 drops the grid condition (A/B runs).
 inline int conv1h_two() {
   static const int v = [] { const char* e = getenv("DS_CONV1_TWO"); return e ? atoi(e) : 1; }();
   return v;
 }
-inline long long conv1h_two_min() {
-  static const long long v = [] { const char* e = getenv("DS_CONV1_TWO_MIN"); return e ? atoll(e) : 256ll; }();
-  return v;
-}
+constexpr long long TWO_MIN_WORKGROUPS = 256;
 
 template <int MODE, bool W16>
 int launch_conv1h(Conv1hArgs a, hipStream_t s) {
   const int two = conv1h_two();
-  if (a.n_cot % 2 == 0 && ((two == 1 && (long long)a.n_blocks / 2 >= conv1h_two_min()) || two == 2)) {
+  if (a.n_cot % 2 == 0 && ((two == 1 && (long long)a.n_blocks / 2 >= TWO_MIN_WORKGROUPS) || two == 2)) {
     const int rc = ds::ensure_dynamic_lds<&k_conv1h<MODE, W16, true>>((int)(LDS_BYTES_TWO), "hipFuncSetAttribute(conv1h two)");
     if (rc != DS_OK) return rc;
     a.n_cot_wg = a.n_cot / 2;

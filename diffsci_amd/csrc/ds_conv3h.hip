@@ -132,16 +132,6 @@ __global__ __launch_bounds__(64 * NW, TWO ? 2 : NW / 2) void k_conv3h(const Conv
     b_u = rest / ny;
   }
   STAMP_PLACE();
-#ifdef DS_STAMP
-  if (a.stagger_ticks) {
-    // Experiment (profiles/r02_stamps_stagger.log: no effect): a phase offset between the two workgroups that share a CU.
-    const unsigned id = blockIdx.x + gridDim.x * (blockIdx.y + gridDim.y * blockIdx.z);
-    if (id >= a.stagger_lo && id < a.stagger_hi) {
-      const unsigned long long t0 = __builtin_amdgcn_s_memrealtime();
-      while (__builtin_amdgcn_s_memrealtime() - t0 < a.stagger_ticks) __builtin_amdgcn_s_sleep(8);
-    }
-  }
-#endif
   const int cot = (int)cot_u * COTS;                   // first channel tile of the workgroup
   const int tile_id = (int)tile_u;
   const int b = (int)b_u;
@@ -303,16 +293,11 @@ __global__ __launch_bounds__(64 * NW, TWO ? 2 : NW / 2) void k_conv3h(const Conv
     f32x4 p[8];
 #pragma unroll
     for (int k = 0; k < 8; ++k) p[k] = pp[8 * h + k];
-#ifdef DS_PRE_UNSCALED       // measurement builds: what does the exponent cost the fused loader?
-#pragma unroll
-    for (int k = 0; k < 8; ++k) xr[i][k] = fast_silu((xr[i][k] - p[k][0]) * p[k][1] + p[k][2]);
-#else
     // the sample's activation exponent rides in the table's fourth column (2^-k, the same in every row; 0 = none): scalar select
     const float inv = p[0][3] == 0.f ? 1.0f : p[0][3];
     ascale.inv_scale = inv;                                          // the epilogue undoes it (unscale_from_inv)
 #pragma unroll
     for (int k = 0; k < 8; ++k) xr[i][k] = ds_h3::fast_silu_scaled((xr[i][k] - p[k][0]) * p[k][1] + p[k][2], inv);
-#endif
   };
   auto x_store_vec = [&](int buf) __attribute__((always_inline)) {
     if constexpr (VEC) {
@@ -587,37 +572,27 @@ __global__ __launch_bounds__(64 * NW, TWO ? 2 : NW / 2) void k_conv3h(const Conv
     auto stage_in = [&](int chunk, int ky) __attribute__((always_inline)) {
       const int g = chunk * 3 + ky;
       if (g + 2 < n_steps) w_fetch(g + 2, (ky + 2) % 3);
-#ifdef DS_STAMP
-      const bool fetch = !a.no_stage;
-#else
-      constexpr bool fetch = true;
-#endif
       if constexpr (IMGIN) {
         // the next patch straight into the other buffer: last read before the barrier that ended the previous step, landed
         // by the barrier that ends the step after this one (__syncthreads waits for the wave's outstanding DMA)
         if (ky == 0 && chunk + 1 < a.n_chunks) x_dma(chunk + 1, (chunk + 1) & 1);
       } else
-      if (fetch && ky == 0 && chunk + 1 < a.n_chunks) { rows_fetch(chunk + 1); x_fetch(chunk + 1); }
+      if (ky == 0 && chunk + 1 < a.n_chunks) { rows_fetch(chunk + 1); x_fetch(chunk + 1); }
       // TWO: the eight waves run one program behind one barrier per step, so unshifted all of them multiply at the same time and all
       // of them activate + split at the same time (profiles/r04_pmc_stalls.log: vector and matrix pipes co-executing 1.7 % of the
       // launch).  Waves 0-3 therefore stage their share of the next patch BEFORE this step's matrix instructions, waves 4-7 (their SIMD
       // partners) after them: each SIMD then holds one vector stream beside one matrix stream in both halves of the step
       // (MI355X_MICROARCH.md, Two waves per SIMD, item 9).  Legal: the patch goes to the OTHER X buffer, which nobody reads in this step.
       if constexpr (TWO && !IMGIN) {
-        if (early_stage && wv < 4 && fetch && ky == 1 && chunk + 1 < a.n_chunks) x_store((chunk & 1) ^ 1);
+        if (early_stage && wv < 4 && ky == 1 && chunk + 1 < a.n_chunks) x_store((chunk & 1) ^ 1);
       }
       __builtin_amdgcn_sched_barrier(0);
     };
     auto stage_out = [&](int chunk, int ky, int xbuf) __attribute__((always_inline)) {
       __builtin_amdgcn_sched_barrier(0);
-#ifdef DS_STAMP
-      const bool store = a.no_stage != 1;
-#else
-      constexpr bool store = true;
-#endif
       if constexpr (!IMGIN) {
-        if (store && ky == 0 && chunk + 1 < a.n_chunks) rows_park(xbuf ^ 1);
-        if (store && ky == 1 && chunk + 1 < a.n_chunks && !(TWO && early_stage && wv < 4)) x_store(xbuf ^ 1);
+        if (ky == 0 && chunk + 1 < a.n_chunks) rows_park(xbuf ^ 1);
+        if (ky == 1 && chunk + 1 < a.n_chunks && !(TWO && early_stage && wv < 4)) x_store(xbuf ^ 1);
       }
       __syncthreads();
     };
@@ -767,14 +742,6 @@ inline bool conv3h_shape16() {
   return on;
 }
 
-// Waves per workgroup.  Default: eight for the fused norm+SiLU loader (its staging VALU work spreads over twice the
-// waves: 3-5 % faster at 64 and 128 channels), four otherwise (at 256 channels the extra LDS operand reads of the
-// eight-wave tiling cost 2-3 %: the kernel is power-limited).  DS_CONV_WAVES=4|8 forces one (A/B runs).
-inline int conv3h_waves(bool pre) {
-  static const int forced = [] { const char* e = getenv("DS_CONV_WAVES"); const int v = e ? atoi(e) : 0; return (v == 4 || v == 8) ? v : 0; }();
-  return forced ? forced : (pre ? 8 : 4);
-}
-
 // Waves of the 16x16x32 variant with the fused loader.  Eight (the staging's vector work spread over twice the waves, as in the
 // 32x32x16 kernel) measured 75.5 -> 76.0 samples/s on one box and 79.6 -> 79.0 on another, ADM-128 33.3 -> 33.45 ms per
 // evaluation: noise.  Default four; DS_CONV_WAVES16=8 selects eight up to 128 input channels (A/B runs).
@@ -785,7 +752,7 @@ inline int conv3h_waves16() {
 
 // Two channel tiles per workgroup (TWO): default for the fused norm + SiLU loader at exactly two channel tiles (the 128-channel
 // level: the activation is otherwise computed once per tile) WHEN the halved grid still fills the chip -- at least
-// DS_CONV_TWO_MIN (256: one per CU) workgroups.  Measured on MI355X: config 5's share (2048 such workgroups per launch)
+// TWO_MIN_WORKGROUPS (256: one per CU).  Measured on MI355X: config 5's share (2048 such workgroups per launch)
 // 9.24 -> 9.13 ms per evaluation with it; a [4, 4, 32, 32] latent on a 32-channel network (a handful of workgroups: their
 // latency is the launch's) 21.85 -> 23.3 ms per 10-step forecast, so not there; the headline's level-1 launches (1024 such workgroups at
 // batch 64): 79.9 -> 80.45 samples/s with it.
@@ -794,10 +761,7 @@ inline int conv3h_two() {
   static const int v = [] { const char* e = getenv("DS_CONV_TWO"); return e ? atoi(e) : 1; }();
   return v;
 }
-inline long long conv3h_two_min() {
-  static const long long v = [] { const char* e = getenv("DS_CONV_TWO_MIN"); return e ? atoll(e) : 256ll; }();
-  return v;
-}
+constexpr long long TWO_MIN_WORKGROUPS = 256;
 
 // 16-byte patch loads (VEC): default on wherever the shape allows; DS_CONV_VEC=0 keeps the one-pixel staging items (A/B runs, and
 // the bit-for-bit comparison of the two staging plans in tools/conv_vec_check.py).
@@ -813,7 +777,7 @@ int launch_conv3h_c(const Conv3hArgs& a, hipStream_t s) {
     vec = conv3h_vec() && a.W % 32 == 0 && a.ox == 0 && a.Cin % KC == 0 && (reinterpret_cast<uintptr_t>(a.in) & 15u) == 0;
   if constexpr (MODE == DS_LOAD_PLAIN) {
     const int two = conv3h_two();
-    if (conv3h_shape16() && a.n_chunks % 2 == 0 && a.n_cot % 2 == 0 && ((two == 1 && PRE && a.n_cot == 2 && (long long)a.tiles_y * a.tiles_x * a.B >= conv3h_two_min()) || two == 2)) {
+    if (conv3h_shape16() && a.n_chunks % 2 == 0 && a.n_cot % 2 == 0 && ((two == 1 && PRE && a.n_cot == 2 && (long long)a.tiles_y * a.tiles_x * a.B >= TWO_MIN_WORKGROUPS) || two == 2)) {
       if constexpr (!W16) { if (vec) return launch_conv3h_w<MODE, W16, PRE, CIRC, 8, true, false, true, true>(a, s); }
       return launch_conv3h_w<MODE, W16, PRE, CIRC, 8, true, false, true>(a, s);
     }
@@ -827,7 +791,11 @@ int launch_conv3h_c(const Conv3hArgs& a, hipStream_t s) {
   }
   // the eight-wave max-pool loader would spill (180 B/lane of scratch at 128 VGPRs: four loads per element in flight): four waves
   if constexpr (MODE == DS_LOAD_MAXPOOL2) return launch_conv3h_w<MODE, W16, PRE, CIRC, 4>(a, s);
-  else return conv3h_waves(PRE) == 8 ? launch_conv3h_w<MODE, W16, PRE, CIRC, 8>(a, s) : launch_conv3h_w<MODE, W16, PRE, CIRC, 4>(a, s);
+  // Waves per workgroup of the 32x32x16 kernel: eight for the fused norm+SiLU loader (its staging VALU work spreads over twice the
+  // waves: 3-5 % faster at 64 and 128 channels), four otherwise (at 256 channels the extra LDS operand reads of the
+  // eight-wave tiling cost 2-3 %: the kernel is power-limited).
+  else if constexpr (PRE) return launch_conv3h_w<MODE, W16, PRE, CIRC, 8>(a, s);
+  else return launch_conv3h_w<MODE, W16, PRE, CIRC, 4>(a, s);
 }
 
 template <int MODE, bool W16, bool PRE>
@@ -912,17 +880,6 @@ int ds_conv2d_h3(float* out, const float* in, const void* w_packed, int wshift, 
   a.n_cot = (Cout + COT - 1) / COT;
   a.n_chunks = (Cin + KC - 1) / KC;
   a.tiles_x_magic = a.tiles_x == 1 ? 0u : (unsigned)((1ull << 32) / (unsigned)a.tiles_x) + 1u;   // tiles_x = 1 is special-cased in the kernel
-#ifdef DS_STAMP
-  {
-    // experiment knob of the stamp build: DS_CONV_STAGGER="ticks[,lo,hi]" (10 ns ticks; default range = the second resident
-    // workgroup of every CU under breadth-first dispatch: indices [256, 512))
-    static const struct Stg { unsigned ticks = 0, lo = 256, hi = 512; Stg() { const char* e = getenv("DS_CONV_STAGGER"); if (e) sscanf(e, "%u,%u,%u", &ticks, &lo, &hi); } } stg;
-    a.stagger_ticks = stg.ticks; a.stagger_lo = stg.lo; a.stagger_hi = stg.hi;
-    // DS_CONV_NOSTAGE=1|2 (16x16x32 variant): what does staging the input patches cost?  (profiles/r02_stamps_nostage.log)
-    static const unsigned nostage = [] { const char* e = getenv("DS_CONV_NOSTAGE"); return e ? (unsigned)atoi(e) : 0u; }();
-    a.no_stage = nostage;
-  }
-#endif
 #ifdef DS_STAMP
   a.stamps = g_stamps;
 #endif

@@ -72,8 +72,6 @@ struct Conv3hArgs {
   int two_early;            // ds_conv3h.hip, two channel tiles per workgroup: waves 0-3 stage the next patch before the step's matrix instructions (DS_CONV_TWO_EARLY)
 #ifdef DS_STAMP
   unsigned long long* stamps;   // diagnostic build only (tools/conv3h_stamp.hip)
-  unsigned stagger_lo, stagger_hi, stagger_ticks;   // experiment: workgroups with dispatch index in [lo, hi) start `ticks` x 10 ns late
-  unsigned no_stage;                                // experiment (wrong results): 1 = the patches after the first are neither fetched nor split / stored, 2 = not fetched
 #endif
 };
 

@@ -24,10 +24,10 @@
 // As shipped at the end of round 4 (second session; every step bit-identical to ds_conv3h.hip):
 //   * staging by 16-byte loads (VEC: a unit = 2 channels x 4 pixels, the fused norm's table rows through LDS pad vectors), the two
 //     kinds of producer wave in their own instantiation of the loop;
-//   * the CONSUMERS issue the weight slabs' DMA at the head of their step (DS_PC_CDMA): a DMA costs its wave 150-200 cycles to issue,
+//   * the CONSUMERS issue the weight slabs' DMA at the head of their step: a DMA costs its wave 150-200 cycles to issue,
 //     the consumers wait for the producers at every barrier anyway, and the producers then have no cross-wave vector-memory wait at all;
 //   * the producers' vector work in slot-thirds, one per step, the previous item's store phase one batch per (E,1) / (O,1) step of the
-//     item's first two chunk pairs (DS_PC_SPREAD);
+//     item's first two chunk pairs;
 //   * IMG: pre-split image input (the 256-channel level) -- the producers issue DMA only (image patches in front of the weight slab).
 //
 // Shapes it takes (the launcher falls back to ds_conv3h.hip otherwise): plain load, 8 x 32 pixel tiles that tile the plane
@@ -85,22 +85,12 @@ __device__ __forceinline__ void bar_counted(int young) {
 #undef DS_VMCNT_CASE
 
 struct Item { int cot, b, y0, x0, tile; };
-#ifndef DS_PC_FETCH_LATE
-#define DS_PC_FETCH_LATE 0
-#endif
-#ifndef DS_PC_SPREAD
-#define DS_PC_SPREAD 1                               // 0: the whole store phase in the item's first chunk pair (measurement builds)
-#endif
-#ifndef DS_PC_IMG_CDMA
-#define DS_PC_IMG_CDMA 0                             // image input: 1 = the consumers issue the weight DMA there too (measurement builds)
-#endif
-#ifndef DS_PC_CDMA
-#define DS_PC_CDMA 1                                 // 0: the producers issue the weight DMA (measurement builds, tools/build_variant.sh)
-#endif
 #define DS_LPI 8                                    // vector-memory loads per staging item
 
-template <int XI> struct Packed { u32x4 h[XI], l[XI]; };
-template <int BK> struct ResRegs { f32x4 r1[BK], r2[BK]; };
+constexpr int XI = 3;                                // staging items per producer thread
+constexpr int BK = 4;                                // store instructions per batch (four batches per wave and item)
+struct Packed { u32x4 h[XI], l[XI]; };
+struct ResRegs { f32x4 r1[BK], r2[BK]; };
 struct Frag { f16x8 a[2][4], b[2][4]; };             // one K = 32 group's operands: [piece][16-channel tile], [piece][16-position tile]
 
 // The weight slabs' LDS-DMA as inline assembly: global_load_lds is FLAT-encoded and touches both memories, which hipcc's wait-count
@@ -123,10 +113,7 @@ __device__ __forceinline__ unsigned const_u32(const void* p, size_t i) {
 // NRES: residual tensors added in the store phase (0, 1 = res1, 2 = res1 and res2) -- a template parameter so that the residual
 // loads are unconditional instructions: hipcc counts only those when it sizes the wait for a loaded register, and a wait sized
 // vmcnt(0) in the store phase also waits for the previous batch's STORES to complete (about 8,000 cycles, stamped).
-// NPW: producer waves, 4 (two waves per SIMD: 256 registers each) or 8 (three per SIMD: 168 registers each; the consumer then keeps
-// ONE operand set and fetches a group's operands right in front of its matrix instructions -- it has the time: the producers pace
-// this kernel -- and every producer wave stages and stores half as much).
-// VEC (four producers): the patch's 32 interior columns are fetched by 16-byte loads, a staging unit = 2 channels x 4 pixels, the two
+// VEC: the patch's 32 interior columns are fetched by 16-byte loads, a staging unit = 2 channels x 4 pixels, the two
 // halo columns keep the one-pixel items in the last slot of producer waves 2 and 3 -- ds_conv3h.hip's VEC plan, lane for lane.  A
 // chunk costs a producer wave 7 or 13 vector-memory loads instead of 24 (their issue paces the fetch steps, see above).  The two kinds of
 // producer wave run their own instantiation of the loop (role 1: three interior slots, role 2: two and a halo slot), so that every load
@@ -135,16 +122,10 @@ __device__ __forceinline__ unsigned const_u32(const void* p, size_t i) {
 // pad vectors of the X buffer the chunk is staged into, at least one barrier before the activation reads them.
 // IMG: the input arrives as pre-split fp16 hi / lo images (ds_inorm_silu_images; ds_conv3h.hip, IMGIN) -- the 256-channel level of
 // config 2.  The producers then only issue DMA: an X buffer is filled by 22 wave-instructions (the one-shot kernel's plan, lane for
-// lane), the weight slabs stay with them too (DS_PC_CDMA applies to the staging forms only), and the consumers are pure matrix streams.
-template <bool PRE, bool CIRC, int NRES, int NPW, bool VEC = false, bool IMG = false>
-__global__ __launch_bounds__(256 + 64 * NPW, NPW == 4 ? 2 : 3) void k_conv3p(const Conv3hArgs a) {
-  static_assert(NPW == 4 || NPW == 8, "four or eight producer waves");
-  static_assert(!VEC || NPW == 4, "16-byte patch loads: the four-producer form");
-  static_assert(!IMG || (!PRE && !CIRC && !VEC && NPW == 4), "image input: plain zero-padded four-producer form");
-  constexpr int XI = NPW == 4 ? 3 : 2;                     // staging items per producer thread
-  constexpr int BK = NPW == 4 ? 4 : 2;                     // store instructions per batch (four batches per wave and item)
-  using Packed = ds_conv3::Packed<XI>;
-  using ResRegs = ds_conv3::ResRegs<BK>;
+// lane), the weight slabs stay with them too (only the staging forms hand them to the consumers), and the consumers are pure matrix streams.
+template <bool PRE, bool CIRC, int NRES, bool VEC = false, bool IMG = false>
+__global__ __launch_bounds__(512, 2) void k_conv3p(const Conv3hArgs a) {
+  static_assert(!IMG || (!PRE && !CIRC && !VEC), "image input: plain zero-padded form");
   constexpr int PW = Geo<false>::PW, NPOS = Geo<false>::NPOS;
   constexpr int HS = NPOS + HPAD16, PS = 2 * NPOS + HPAD16, XBV = XBUF_VEC16;
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -158,8 +139,6 @@ __global__ __launch_bounds__(256 + 64 * NPW, NPW == 4 ? 2 : 3) void k_conv3p(con
   const int rw = wv & 3;                                   // consumer: its row pair; producer: the consumer whose tile it stores
   const int ptid = tid - 256;                              // producer thread (negative in the consumer waves: unused there)
   const int pw = wv - 4;                                   // producer wave
-  const int rws = NPW == 4 ? rw : ((pw >> 1) & 3);         // the consumer whose tile this producer stores
-  const int joff = NPW == 4 ? 0 : 8 * (pw & 1);            // ... and its first store instruction (eight producers: 32 channels each)
 
   // ---- this workgroup's items: XCD x owns one contiguous run of the logical order (channel tile fastest, then pixel tile, then
   //      sample), dealt round-robin over the Q workgroups of the XCD, so the workgroups of an XCD work on neighbouring tiles ----
@@ -266,18 +245,17 @@ __global__ __launch_bounds__(256 + 64 * NPW, NPW == 4 ? 2 : 3) void k_conv3p(con
   // =========================== producer ===========================
   // staging items of a thread (ds_conv3h.hip's four-wave plan over the 256 producer threads): items 0 / 1 = position ptid of
   // channel half 0 / 1, item 2 = the patch's tail (positions 256 ..), half (producer wave / 2)
-  // eight producers: waves 0-3 channel half 0, waves 4-7 half 1; item 0 = positions 64 (pw & 3) + lane, item 1 = the tail,
-  // 21 positions per wave (256 + 21 (pw & 3) + lane, lanes 0-20)
   const int tail_h = (rw >> 1) & 1;
-  auto item_h = [&](int i) __attribute__((always_inline)) { return NPW == 8 ? ((pw >> 2) & 1) : (i == 0 ? 0 : (i == 1 ? 1 : tail_h)); };
+  // ((void)pw keeps pw among this closure's captures.  Nothing computes with it, but hipcc's order of three zero-initialising moves in
+  // the prologue of the six plain one-pixel kernels depends on it, and with it every kernel of this file is instruction for
+  // instruction the code that was measured: DESIGN.md 4.5.  It goes when the start-up stagger and the producer priority go: that alters every body.)
+  auto item_h = [&](int i) __attribute__((always_inline)) { (void)pw; return i == 0 ? 0 : (i == 1 ? 1 : tail_h); };
   int xlds[XI], xrow[XI], xcol[XI];
-  const bool live_tail = NPW == 4 ? (NT + (ptid & (NT / 2 - 1)) < NPOS) : (lane < 21);     // the thread's tail item exists
+  const bool live_tail = NT + (ptid & (NT / 2 - 1)) < NPOS;     // the thread's tail item exists
   auto live = [&](int i) __attribute__((always_inline)) { return i < XI - 1 || live_tail; };
 #pragma unroll
   for (int i = 0; i < XI; ++i) {
-    int pos;
-    if (NPW == 4) pos = i < 2 ? (ptid & 255) : NT + (ptid & (NT / 2 - 1));
-    else pos = i == 0 ? 64 * (pw & 3) + lane : 256 + 21 * (pw & 3) + (lane < 21 ? lane : 20);
+    const int pos = i < 2 ? (ptid & 255) : NT + (ptid & (NT / 2 - 1));
     xrow[i] = pos / PW;
     xcol[i] = pos - xrow[i] * PW;
     xlds[i] = item_h(i) * HS + pos;
@@ -505,21 +483,6 @@ __global__ __launch_bounds__(256 + 64 * NPW, NPW == 4 ? 2 : 3) void k_conv3p(con
   // the loads of chunk n beside the vector work of the LAST slot of chunk o (whose other slots were activated a step earlier)
   auto fetch_beside_last_slot = [&](auto halo_tag, float (&xn)[XI][8], f32x4& prown, unsigned& tagn, int& trown, float& tscn,
                                     float (&xo)[XI][8], unsigned tago, int trowo, float tsco, Packed& pk, int bufo) __attribute__((always_inline)) {
-#if DS_PC_FETCH_LATE == 1   // measurement builds: the vector work first, the loads behind it (+3.5 %, profiles/r04_pc_smooth_schedule.log) ...
-    activate_item(halo_tag, xo, tago, trowo, tsco, pk, XI - 1, bufo);
-    __builtin_amdgcn_sched_barrier(0);
-    fetch_begin(tagn, trown, tscn);
-    rows_fetch(prown, trown);
-#pragma unroll
-    for (int i = 0; i < XI; ++i) fetch_item(halo_tag, xn, i);
-#elif DS_PC_FETCH_LATE == 2   // ... or every load in front of it
-    fetch_begin(tagn, trown, tscn);
-    rows_fetch(prown, trown);
-#pragma unroll
-    for (int i = 0; i < XI; ++i) fetch_item(halo_tag, xn, i);
-    __builtin_amdgcn_sched_barrier(0);
-    activate_item(halo_tag, xo, tago, trowo, tsco, pk, XI - 1, bufo);
-#else
     fetch_begin(tagn, trown, tscn);
     rows_fetch(prown, trown);
 #pragma unroll
@@ -528,7 +491,6 @@ __global__ __launch_bounds__(256 + 64 * NPW, NPW == 4 ? 2 : 3) void k_conv3p(con
     activate_item(halo_tag, xo, tago, trowo, tsco, pk, XI - 1, bufo);
     __builtin_amdgcn_sched_barrier(0);
     fetch_item(halo_tag, xn, XI - 1);
-#endif
     return fetch_count(halo_tag);
   };
   auto store_x = [&](auto halo_tag, const Packed& pk, unsigned tag, int buf) __attribute__((always_inline)) {
@@ -564,18 +526,18 @@ __global__ __launch_bounds__(256 + 64 * NPW, NPW == 4 ? 2 : 3) void k_conv3p(con
   };
   // weight cursor: the next slab to DMA.  Unconditional as well (past the end: the last item's first slab into a slot nobody reads).
   int w_k = 0, w_step = 0, w_cot = 0;
-  // widx / nwv: the issuing wave's index among the nwv waves that share a slab's twelve pieces -- the producers, or (cdma) the four
+  // widx: the issuing wave's index among the four waves that share a slab's twelve pieces -- the producers, or (cdma) the
   // CONSUMERS: a weight DMA costs its wave 150-200 cycles to issue (stamped), three per step; the producers pace this kernel and the
   // consumers wait for them at every barrier, so the consumers issue them, in front of the step's matrix instructions
-  constexpr bool cdma = DS_PC_CDMA != 0 && (!IMG || DS_PC_IMG_CDMA != 0);            // compile time (as a kernel argument the two forms side by side cost 15 % -- measured)
-  auto wdma = [&](int slot, int widx, int nwv) __attribute__((always_inline)) {     // slot = (slab index) & 3
+  constexpr bool cdma = !IMG;            // image input: the producers issue the weight DMA too.  Compile time (as a kernel argument the two forms side by side cost 15 % -- measured)
+  auto wdma = [&](int slot, int widx) __attribute__((always_inline)) {     // slot = (slab index) & 3
     const bool valid = w_k < n_items;
     if (valid && w_step == 0) w_cot = item_of(w_k).cot;
     const u32x4* src = a.wp + ((size_t)w_cot * n_steps + w_step) * WSLAB_VEC;
     u32x4* dst = Ws + slot * WSLAB_VEC;
 #pragma unroll
     for (int i = 0; i < 3; ++i) {
-      const int k = widx + nwv * i;                   // wave-uniform piece of the slab's twelve
+      const int k = widx + 4 * i;                     // wave-uniform piece of the slab's twelve
       if (k < 12) lds_dma16(src + 64 * k, 16u * (unsigned)lane, lds_address(dst + 64 * k));
     }
     if (valid && ++w_step == n_steps) { w_step = 0; ++w_k; }
@@ -607,7 +569,6 @@ __global__ __launch_bounds__(256 + 64 * NPW, NPW == 4 ? 2 : 3) void k_conv3p(con
   // (ds_conv_epilogue.h: store_tile_rows' aligned path, full tiles).  The wave's statistics partials [64 channels][4] go to the
   // head of its own tile, behind the batch that has just read it.
   int s_b = 0, s_cot = 0, s_tile = 0;
-  f32x4 pend0[BK];                                   // eight producers: the statistics rows of batch 0, written with batch 1 (store_batch)
   size_t s_idx = 0;                                  // the lane's first output element
   const size_t s_step = 4 * (size_t)HW;
   float s_amax = 0.f;
@@ -616,8 +577,8 @@ __global__ __launch_bounds__(256 + 64 * NPW, NPW == 4 ? 2 : 3) void k_conv3p(con
   constexpr int nres = BK * NRES;
   auto plan_store = [&](const Item& it) __attribute__((always_inline)) {
     s_b = it.b; s_cot = it.cot; s_tile = it.tile;
-    const int gy = it.y0 + 2 * rws + ((lane >> 3) & 1), gx = it.x0 + p4;
-    const size_t ch = (size_t)it.b * a.Cout + it.cot * COT + 4 * joff + (lane >> 4);
+    const int gy = it.y0 + 2 * rw + ((lane >> 3) & 1), gx = it.x0 + p4;
+    const size_t ch = (size_t)it.b * a.Cout + it.cot * COT + (lane >> 4);
     s_idx = ch * HW + (size_t)gy * a.W + gx;
     s_amax = 0.f;
   };
@@ -633,11 +594,11 @@ __global__ __launch_bounds__(256 + 64 * NPW, NPW == 4 ? 2 : 3) void k_conv3p(con
     return nres;
   };
   auto store_batch = [&](const ResRegs& R, int half) __attribute__((always_inline)) {
-    float* tile = OUT + rws * 4096;
+    float* tile = OUT + rw * 4096;
     f32x4 v[BK];
 #pragma unroll
     for (int k = 0; k < BK; ++k) {
-      const int seg = (joff + half * BK + k) * 8 + (lane >> 3);
+      const int seg = (half * BK + k) * 8 + (lane >> 3);
       v[k] = *reinterpret_cast<const f32x4*>(&tile[seg * 32 + p4]);
     }
     if constexpr (NRES >= 1) {
@@ -664,19 +625,11 @@ __global__ __launch_bounds__(256 + 64 * NPW, NPW == 4 ? 2 : 3) void k_conv3p(con
         const float qv = ds_epi::row16_sum((d.x * d.x + d.y * d.y) + (d.z * d.z + d.w * d.w));
         o[k] = f32x4{K, sv, qv, 64.f};                                   // the wave's 2 x 32 pixels of the channel
       }
-      // row (channel) 4 j + lane / 16 of [64][4] at the tile's head, i.e. inside the region store instructions 0-3 read.  Four producers:
-      // that is this wave's own batch 0, read by now.  Eight producers: it is the FIRST wave's batches 0 / 1 -- the second wave of a
-      // tile (and, for one rule, the first) holds its batch-0 rows back until its batch 1, which the schedule runs a barrier later
-      if (NPW == 8 && half == 0) {
+      // row (channel) 4 j + lane / 16 of [64][4] at the tile's head, i.e. inside the region store instructions 0-3 read: this wave's
+      // own batch 0, read by now
+      if ((lane & 15) == 0) {
 #pragma unroll
-        for (int k = 0; k < BK; ++k) pend0[k] = o[k];
-      } else if ((lane & 15) == 0) {
-        if (NPW == 8 && half == 1) {
-#pragma unroll
-          for (int k = 0; k < BK; ++k) *reinterpret_cast<f32x4*>(&tile[4 * (4 * (joff + k) + (lane >> 4))]) = pend0[k];
-        }
-#pragma unroll
-        for (int k = 0; k < BK; ++k) *reinterpret_cast<f32x4*>(&tile[4 * (4 * (joff + half * BK + k) + (lane >> 4))]) = o[k];
+        for (int k = 0; k < BK; ++k) *reinterpret_cast<f32x4*>(&tile[4 * (4 * (half * BK + k) + (lane >> 4))]) = o[k];
       }
     }
     return BK;
@@ -728,7 +681,7 @@ __global__ __launch_bounds__(256 + 64 * NPW, NPW == 4 ? 2 : 3) void k_conv3p(con
     // everything else of step p + 1 (`young`) may stay in flight.  Loads, LDS-DMA and stores complete in issue order on gfx9
     // (hipcc's own counted waits rely on it), so "all but the N youngest" names exactly the operations in front of them.
     int young = 0, prev = 0, nx = 0;                  // nx (IMG): this step's image DMA, issued in front of its weight DMA
-    const int ndma = NPW == 4 ? 3 : (pw < 4 ? 2 : 1);             // DMA instructions of this wave per step
+    constexpr int ndma = 3;                           // DMA instructions of this wave per step
     auto barrier = [&]() __attribute__((always_inline)) {
       // (cdma: a consumer's only vector-memory operations are its three DMA per step -- those of the step that ends here may stay in
       //  flight, the previous step's have landed; the producers then have nothing another wave waits for)
@@ -752,7 +705,7 @@ __global__ __launch_bounds__(256 + 64 * NPW, NPW == 4 ? 2 : 3) void k_conv3p(con
     //   (O,0)  fetch chunk O+2 -> A  beside  the last slot of chunk E+2 | batch 2, residuals of batch 3 | next item's bias / shift loads
     //   (O,1)  store chunk E+2 -> X0, park chunk O+2's table rows | batch 3, output maxima
     //   (O,2)  activate + split the first slots of chunk O+2 (A) | statistics combine | commit the next item's bias / shift row
-    // (+ the slab's DMA at the head of every step when the producers issue it: DS_PC_CDMA=0.)  One slot-third of the vector work per
+    // (+ the slab's DMA at the head of every step when the producers issue it: image input.)  One slot-third of the vector work per
     // step instead of a whole chunk in (E,0) and in (O,1): the consumer's steps are 1-2 K = 32 groups long, and a step lasts as long
     // as the slower role (round 4, second session: profiles/r04_pc_smooth_schedule.log).
     // (batches = the PREVIOUS item's store phase, on the item's first chunk pair only.)  What a group reads is published one
@@ -762,10 +715,9 @@ __global__ __launch_bounds__(256 + 64 * NPW, NPW == 4 ? 2 : 3) void k_conv3p(con
     //  +1.6 % for this one): with both chunks' 48 loads issued in consecutive steps next to the residual loads and stores the wave
     //  runs into its 64 outstanding vector-memory operations and the loads' issue stalls.]
     // head / second: the item's first / second chunk pair.  The previous item's store phase -- four batches of stores, residual
-    // loads, statistics -- runs on the producers one batch per (E,1) / (O,1) step of these TWO pairs (DS_PC_SPREAD; every item has
+    // loads, statistics -- runs on the producers one batch per (E,1) / (O,1) step of these TWO pairs (every item has
     // at least two): a batch costs its wave 1,000-2,000 cycles, and with all four in the first pair's steps (E,1) .. (O,1) that
     // pair took 19,400 cycles against 12,200 for the others (profiles/r04_pc_smooth_schedule.log)
-    constexpr bool SPREAD = DS_PC_SPREAD != 0;
     auto chunk_pair = [&](auto base_tag, Frag& Fa, Frag& Fb, bool head, bool second, bool last_of_item, int it) __attribute__((always_inline)) {
       constexpr int B = decltype(base_tag)::value;
       constexpr int E0 = (B + 0) & 3, E1 = (B + 1) & 3, E2 = (B + 2) & 3;          // ring slots of chunk E's slabs
@@ -775,30 +727,24 @@ __global__ __launch_bounds__(256 + 64 * NPW, NPW == 4 ? 2 : 3) void k_conv3p(con
       constexpr int G[10][8] = {{E0, 0, 0, 0, E0, 0, 1, 0}, {E0, 0, 2, 0, E1, 1, 0, 0}, {E1, 1, 1, 0, E1, 1, 2, 0}, {E2, 2, 0, 0, E2, 2, 1, 0},
                                 {E2, 2, 2, 0, O0, 0, 0, 1}, {O0, 0, 1, 1, O0, 0, 2, 1}, {O1, 1, 0, 1, O1, 1, 1, 1}, {O1, 1, 2, 1, O2, 2, 0, 1},
                                 {O2, 2, 1, 1, O2, 2, 2, 1}, {N0, 0, 0, 0, N0, 0, 1, 0}};
-      // group k: four producers -- multiply the set fetched during group k - 1 while fetching group k + 1 into the other set;
-      // eight producers -- one set: fetch, then multiply
+      // group k: multiply the set fetched during group k - 1 while fetching group k + 1 into the other set
       auto group = [&](auto k_tag) __attribute__((always_inline)) {
         constexpr int k = decltype(k_tag)::value;
-        if constexpr (NPW == 4) {
-          Frag& cur = (k & 1) ? Fb : Fa;
-          Frag& nxt = (k & 1) ? Fa : Fb;
-          load_pair(nxt, G[k + 1][0], G[k + 1][1], G[k + 1][2], G[k + 1][3], G[k + 1][4], G[k + 1][5], G[k + 1][6], G[k + 1][7]);
-          mma_pair(cur);
-          reads_between();
-        } else {
-          load_pair(Fa, G[k][0], G[k][1], G[k][2], G[k][3], G[k][4], G[k][5], G[k][6], G[k][7]);
-          mma_pair(Fa);
-        }
+        Frag& cur = (k & 1) ? Fb : Fa;
+        Frag& nxt = (k & 1) ? Fa : Fb;
+        load_pair(nxt, G[k + 1][0], G[k + 1][1], G[k + 1][2], G[k + 1][3], G[k + 1][4], G[k + 1][5], G[k + 1][6], G[k + 1][7]);
+        mma_pair(cur);
+        reads_between();
       };
 #define DS_GROUP(k) group(std::integral_constant<int, k>{})
       // ---------------- step (E, 0) ----------------
       if constexpr (CONS) {
-        if (cdma) { wdma((B + 3) & 3, rw, 4); __builtin_amdgcn_sched_barrier(0); }
+        if (cdma) { wdma((B + 3) & 3, rw); __builtin_amdgcn_sched_barrier(0); }
         if (head) park_tile((it - 1) & 1);
         DS_GROUP(0); DS_GROUP(1);
       } else {
         if constexpr (IMG) nx = xdma(1);              // chunk O -> X1: free since the barrier of the previous (O, 2), read from (E, 2) on
-        if (!cdma) wdma((B + 3) & 3, pw, NPW);
+        if (!cdma) wdma((B + 3) & 3, pw);
         __builtin_amdgcn_sched_barrier(0);
         if (head) { plan_store(item_of(it - 1)); young += res_prefetch(RA, 0); }
         if constexpr (!IMG) {
@@ -811,10 +757,10 @@ __global__ __launch_bounds__(256 + 64 * NPW, NPW == 4 ? 2 : 3) void k_conv3p(con
       barrier();
       // ---------------- step (E, 1) ----------------
       if constexpr (CONS) {
-        if (cdma) { wdma((B + 4) & 3, rw, 4); __builtin_amdgcn_sched_barrier(0); }
+        if (cdma) { wdma((B + 4) & 3, rw); __builtin_amdgcn_sched_barrier(0); }
         DS_GROUP(2);
       } else {
-        if (!cdma) wdma((B + 4) & 3, pw, NPW);
+        if (!cdma) wdma((B + 4) & 3, pw);
         __builtin_amdgcn_sched_barrier(0);
         if constexpr (!IMG) {
           store_x(halo, pk, tagP, 1);
@@ -824,51 +770,37 @@ __global__ __launch_bounds__(256 + 64 * NPW, NPW == 4 ? 2 : 3) void k_conv3p(con
           young += store_batch(RA, 0);
           young += res_prefetch(RB, 1);
         }
-        if constexpr (SPREAD) {
-          if (second) { young += store_batch(RA, 2); young += res_prefetch(RB, 3); }
-        }
+        if (second) { young += store_batch(RA, 2); young += res_prefetch(RB, 3); }
       }
       if (stamp < 48) PSTAMP(stamp);
       ++stamp;
       barrier();
       // ---------------- step (E, 2) ----------------
       if constexpr (CONS) {
-        if (cdma) { wdma((B + 5) & 3, rw, 4); __builtin_amdgcn_sched_barrier(0); }
+        if (cdma) { wdma((B + 5) & 3, rw); __builtin_amdgcn_sched_barrier(0); }
         DS_GROUP(3); DS_GROUP(4);
       } else {
-        if (!cdma) wdma((B + 5) & 3, pw, NPW);
+        if (!cdma) wdma((B + 5) & 3, pw);
         __builtin_amdgcn_sched_barrier(0);
         if constexpr (!IMG) activate_first_slots(halo, xrB, tagB, trowB, tscB, pk, 0);      // chunk E + 2 (fetched in (E, 0), rows parked in (E, 1))
         __builtin_amdgcn_sched_barrier(0);
-        if constexpr (!SPREAD) {
-          if (head) {
-            young += store_batch(RB, 1);
-            young += res_prefetch(RA, 2);
-          }
-        }
       }
       if (stamp < 48) PSTAMP(stamp);
       ++stamp;
       barrier();
       // ---------------- step (O, 0) ----------------
       if constexpr (CONS) {
-        if (cdma) { wdma((B + 6) & 3, rw, 4); __builtin_amdgcn_sched_barrier(0); }
+        if (cdma) { wdma((B + 6) & 3, rw); __builtin_amdgcn_sched_barrier(0); }
         DS_GROUP(5);
       } else {
         PSTAMP_FINE(0);
         if constexpr (IMG) nx = xdma(0);              // chunk E + 2 -> X0: free since the barrier of (E, 2), read from (O, 2) on
-        if (!cdma) wdma((B + 6) & 3, pw, NPW);
+        if (!cdma) wdma((B + 6) & 3, pw);
         __builtin_amdgcn_sched_barrier(0);
         PSTAMP_FINE(1);
         if constexpr (!IMG) young += fetch_beside_last_slot(halo, xrA, prowA, tagA, trowA, tscA, xrB, tagB, trowB, tscB, pk, 0);       // chunk O + 2 | chunk E + 2's last slot
         __builtin_amdgcn_sched_barrier(0);
         PSTAMP_FINE(2);
-        if constexpr (!SPREAD) {
-          if (head) {
-            young += store_batch(RA, 2);
-            young += res_prefetch(RB, 3);
-          }
-        }
         if (last_of_item && it + 1 < n_items) bs_fetch(item_of(it + 1), bsb, bss);
       }
       if (stamp < 48) PSTAMP(stamp);
@@ -876,11 +808,11 @@ __global__ __launch_bounds__(256 + 64 * NPW, NPW == 4 ? 2 : 3) void k_conv3p(con
       barrier();
       // ---------------- step (O, 1) ----------------
       if constexpr (CONS) {
-        if (cdma) { wdma((B + 7) & 3, rw, 4); __builtin_amdgcn_sched_barrier(0); }
+        if (cdma) { wdma((B + 7) & 3, rw); __builtin_amdgcn_sched_barrier(0); }
         DS_GROUP(6); DS_GROUP(7);
       } else {
         PSTAMP_FINE(4);
-        if (!cdma) wdma((B + 7) & 3, pw, NPW);
+        if (!cdma) wdma((B + 7) & 3, pw);
         __builtin_amdgcn_sched_barrier(0);
         PSTAMP_FINE(5);
         if constexpr (!IMG) {
@@ -888,29 +820,22 @@ __global__ __launch_bounds__(256 + 64 * NPW, NPW == 4 ? 2 : 3) void k_conv3p(con
           rows_park(prowA, 1);                        // chunk O + 2's table rows: read by its activation from (O, 2) on
         }
         PSTAMP_FINE(6);
-        if constexpr (SPREAD) {
-          if (head) { young += store_batch(RB, 1); young += res_prefetch(RA, 2); }
-          if (second) { young += store_batch(RB, 3); if (want_amax) commit_amax_asm(); }
-        } else {
-          if (head) {
-            young += store_batch(RB, 3);
-            if (want_amax) commit_amax_asm();
-          }
-        }
+        if (head) { young += store_batch(RB, 1); young += res_prefetch(RA, 2); }
+        if (second) { young += store_batch(RB, 3); if (want_amax) commit_amax_asm(); }
       }
       if (stamp < 48) PSTAMP(stamp);
       ++stamp;
       barrier();
       // ---------------- step (O, 2) ----------------
       if constexpr (CONS) {
-        if (cdma) { wdma((B + 8) & 3, rw, 4); __builtin_amdgcn_sched_barrier(0); }
+        if (cdma) { wdma((B + 8) & 3, rw); __builtin_amdgcn_sched_barrier(0); }
         DS_GROUP(8);
       } else {
-        if (!cdma) wdma((B + 8) & 3, pw, NPW);
+        if (!cdma) wdma((B + 8) & 3, pw);
         __builtin_amdgcn_sched_barrier(0);
         if constexpr (!IMG) activate_first_slots(halo, xrA, tagA, trowA, tscA, pk, 1);      // chunk O + 2 (fetched in (O, 0), rows parked in (O, 1))
         __builtin_amdgcn_sched_barrier(0);
-        if ((SPREAD ? second : head) && stats && wv == 4) store_stats();  // the four waves' batch-3 partials are behind the barrier of (O, 1)
+        if (second && stats && wv == 4) store_stats();  // the four waves' batch-3 partials are behind the barrier of (O, 1)
         if (last_of_item && it + 1 < n_items) bs_commit(bsb, bss, unscale_of(item_of(it + 1)), (it + 1) & 1);
       }
       if (stamp < 48) PSTAMP(stamp);
@@ -929,7 +854,7 @@ __global__ __launch_bounds__(256 + 64 * NPW, NPW == 4 ? 2 : 3) void k_conv3p(con
     // ---- prologue: slabs 0, 1, 2, chunk 0 in X buffer 0, chunk 1 in flight, the first item's bias / shift row ----
     if constexpr (!CONS) {
       if constexpr (IMG) xdma(0);                     // chunk 0 -> X0 (chunk 1 follows in the first (E, 0))
-      if (!cdma) { wdma(0, pw, NPW); wdma(1, pw, NPW); wdma(2, pw, NPW); }
+      if (!cdma) { wdma(0, pw); wdma(1, pw); wdma(2, pw); }
       if constexpr (!IMG) {
         fetch(halo, xrB, prowB, tagB, trowB, tscB);
         fetch(halo, xrA, prowA, tagA, trowA, tscA);
@@ -952,7 +877,7 @@ __global__ __launch_bounds__(256 + 64 * NPW, NPW == 4 ? 2 : 3) void k_conv3p(con
       if constexpr (VEC || IMG) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
       else asm volatile("s_waitcnt vmcnt(20)" ::: "memory");     // the three slabs and chunk 0; chunk 1's loads may stay in flight (the bias / shift loads are younger still)
     } else {
-      if (cdma) { wdma(0, rw, 4); wdma(1, rw, 4); wdma(2, rw, 4); }
+      if (cdma) { wdma(0, rw); wdma(1, rw); wdma(2, rw); }
       if constexpr (VEC && PRE) asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");     // the producers' table-row barrier
 #pragma unroll
       for (int m = 0; m < 4; ++m)
@@ -965,14 +890,13 @@ __global__ __launch_bounds__(256 + 64 * NPW, NPW == 4 ? 2 : 3) void k_conv3p(con
     if constexpr (CONS) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");            // (cdma) the first three slabs
     asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
     young = 0; prev = (VEC || IMG) ? 0 : DS_LPI * XI;          // behind the prologue's slabs: chunk 1's loads (VEC: the prologue waited for everything)
-    if constexpr (CONS && NPW == 4) load_pair(F0, 0, 0, 0, 0, 0, 0, 1, 0);         // P0 of the first chunk pair
+    if constexpr (CONS) load_pair(F0, 0, 0, 0, 0, 0, 0, 1, 0);         // P0 of the first chunk pair
 
     const int ncp = n_chunks >> 1;                    // even (the launcher's rule): fragment sets and ring slots are back in place after an item
     for (int it = 0; it < n_items; ++it) {
       for (int cp = 0; cp < ncp; cp += 2) {
         chunk_pair(std::integral_constant<int, 0>{}, F0, F1, cp == 0 && it > 0, false, false, it);
-        if constexpr (NPW == 4) chunk_pair(std::integral_constant<int, 6>{}, F1, F0, false, cp == 0 && it > 0, cp + 2 == ncp, it);
-        else chunk_pair(std::integral_constant<int, 6>{}, F0, F1, false, cp == 0 && it > 0, cp + 2 == ncp, it);
+        chunk_pair(std::integral_constant<int, 6>{}, F1, F0, false, cp == 0 && it > 0, cp + 2 == ncp, it);
       }
     }
     // ---- drain: the last item's store phase (its own barriers, nothing staged, nothing multiplied) ----
@@ -987,7 +911,7 @@ __global__ __launch_bounds__(256 + 64 * NPW, NPW == 4 ? 2 : 3) void k_conv3p(con
       store_batch(RA, 0);
       res_prefetch(RB, 1);
     }
-    bar_counted(0);                                   // (eight producers: batch 1 writes the statistics rows batch 0 held back)
+    bar_counted(0);
     if constexpr (!CONS) {
       store_batch(RB, 1);
       res_prefetch(RA, 2);
@@ -1014,17 +938,11 @@ __global__ __launch_bounds__(256 + 64 * NPW, NPW == 4 ? 2 : 3) void k_conv3p(con
   }
 }
 
-// DS_CONV_PC_WAVES = 4 | 8: producer waves per workgroup (A/B runs; the default is what measured faster)
-int conv3p_producer_waves() {
-  static const int v = [] { const char* e = getenv("DS_CONV_PC_WAVES"); const int n = e ? atoi(e) : 4; return n == 8 ? 8 : 4; }();
-  return v;
-}
-
-template <bool PRE, bool CIRC, int NRES, int NPW, bool VEC = false, bool IMG = false>
+template <bool PRE, bool CIRC, int NRES, bool VEC = false, bool IMG = false>
 int launch_conv3p_w(const Conv3hArgs& a, int wgs, hipStream_t s) {
-  const int rc = ds::ensure_dynamic_lds<&k_conv3p<PRE, CIRC, NRES, NPW, VEC, IMG>>(P_LDS, "hipFuncSetAttribute(conv3p)");
+  const int rc = ds::ensure_dynamic_lds<&k_conv3p<PRE, CIRC, NRES, VEC, IMG>>(P_LDS, "hipFuncSetAttribute(conv3p)");
   if (rc != DS_OK) return rc;
-  hipLaunchKernelGGL((k_conv3p<PRE, CIRC, NRES, NPW, VEC, IMG>), dim3((unsigned)wgs), dim3(256 + 64 * NPW), P_LDS, s, a);
+  hipLaunchKernelGGL((k_conv3p<PRE, CIRC, NRES, VEC, IMG>), dim3((unsigned)wgs), dim3(512), P_LDS, s, a);
   DS_CHECK_LAUNCH("ds_conv2d_h3 (persistent)");
   return DS_OK;
 }
@@ -1035,10 +953,9 @@ bool conv3p_vec() {
 }
 template <bool PRE, bool CIRC, int NRES>
 int launch_conv3p_r(const Conv3hArgs& a, int wgs, hipStream_t s) {
-  if (conv3p_producer_waves() == 8) return launch_conv3p_w<PRE, CIRC, NRES, 8>(a, wgs, s);
   // 16-byte patch loads: W is a multiple of 32 and Cin of 64 here (conv3p_try_launch); no column tap offset, an aligned input
-  if (conv3p_vec() && a.ox == 0 && (reinterpret_cast<uintptr_t>(a.in) & 15u) == 0) return launch_conv3p_w<PRE, CIRC, NRES, 4, true>(a, wgs, s);
-  return launch_conv3p_w<PRE, CIRC, NRES, 4>(a, wgs, s);
+  if (conv3p_vec() && a.ox == 0 && (reinterpret_cast<uintptr_t>(a.in) & 15u) == 0) return launch_conv3p_w<PRE, CIRC, NRES, true>(a, wgs, s);
+  return launch_conv3p_w<PRE, CIRC, NRES>(a, wgs, s);
 }
 void conv3p_fill_args(Conv3hArgs& a) {
   a.ntiles_magic40 = (1ull << 40) / (unsigned long long)(a.tiles_x * a.tiles_y) + 1ull;
@@ -1093,7 +1010,7 @@ int conv3p_cus() {
 int conv3p_try_launch_img(const Conv3hArgs& a0, hipStream_t s, bool* launched) {
   *launched = false;
   static const bool on = [] { const char* e = getenv("DS_CONV_PC_IMG"); return !(e && atoi(e) == 0); }();
-  if (!on || conv3p_mode() == 0 || conv3p_producer_waves() != 4) return DS_OK;
+  if (!on || conv3p_mode() == 0) return DS_OK;
   if (a0.H % 8 != 0 || a0.W % 32 != 0 || a0.Cout % COT != 0 || a0.Cin % (4 * KC) != 0 || a0.res1_up) return DS_OK;
   const long long total = (long long)a0.n_cot * a0.tiles_x * a0.tiles_y * a0.B;
   const int wgs = conv3p_cus() / 8 * 8;
@@ -1102,8 +1019,8 @@ int conv3p_try_launch_img(const Conv3hArgs& a0, hipStream_t s, bool* launched) {
   Conv3hArgs a = a0;
   conv3p_fill_args(a);
   int rc;
-  if (!a.res1) rc = launch_conv3p_w<false, false, 0, 4, false, true>(a, wgs, s);
-  else rc = a.res2 ? launch_conv3p_w<false, false, 2, 4, false, true>(a, wgs, s) : launch_conv3p_w<false, false, 1, 4, false, true>(a, wgs, s);
+  if (!a.res1) rc = launch_conv3p_w<false, false, 0, false, true>(a, wgs, s);
+  else rc = a.res2 ? launch_conv3p_w<false, false, 2, false, true>(a, wgs, s) : launch_conv3p_w<false, false, 1, false, true>(a, wgs, s);
   if (rc == DS_OK) *launched = true;
   return rc;
 }

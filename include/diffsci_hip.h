@@ -27,16 +27,13 @@
  * Environment (read once per process; measurement switches, results are identical up to fp32 rounding of the accumulation
  * order): DIFFSCI_HIP_LIB = path of another build of this library (A/B runs, diffsci_amd/_native.py); DS_CONV_SHAPE=32 =
  * the v_mfma_f32_32x32x16_f16 form of ds_conv2d_h3 / ds_conv2d_h3_up everywhere (default: 16x16x32 wherever the layer has
- * an even number of 16-channel chunks); DS_CONV_WAVES=4|8 = waves per workgroup of the 32x32x16 form (default: 8 with the
- * fused loader); DS_CONV_WAVES16=8 = eight waves for the 16x16x32 form with the fused loader (default 4); DS_ATTN_T =
- * rescaling threshold of ds_attention_h3's online softmax (default 8); DS_CONV_PC = 0|1|2|3 = which launches of ds_conv2d_h3 take the
+ * an even number of 16-channel chunks); DS_CONV_WAVES16=8 = eight waves for the 16x16x32 form with the fused loader (default 4); DS_CONV_PC = 0|1|2|3 = which launches of ds_conv2d_h3 take the
  * persistent producer / consumer form (ds_conv3p.hip: 0 none, 1 fused-loader launches with one channel tile, 2 (default) also those
  * with several, 3 raw-input launches too; bit-identical results), DS_CONV_PC_MIN = fewest items per workgroup for it (default 1),
  * DS_CONV_PC_IMG=0 = ds_conv2d_h3_img stays on the one-shot kernel, DS_CONV_PC_SKEW = mask of the persistent kernel's start-up stagger
- * (default 0), DS_CONV_PC_PRIO = s_setprio level of its producer waves (default 0), DS_CONV_PC_WAVES=8 = eight producer waves (the
- * one-pixel staging plan only); DS_CONV_VEC=0 = one-pixel staging items instead of the 16-byte patch loads (both kernels),
- * DS_CONV_TWO=0|1|2 / DS_CONV_TWO_MIN / DS_CONV_TWO_EARLY=0 = the two-channel-tile one-shot kernel: off | two tiles | every even
- * count; its smallest grid; waves 0-3 staging after the step's matrix instructions like waves 4-7; DS_DIRECT_VEC=0 = ds_conv2d_direct's
+ * (default 0), DS_CONV_PC_PRIO = s_setprio level of its producer waves (default 0); DS_CONV_VEC=0 = one-pixel staging items instead of the 16-byte patch loads (both kernels),
+ * DS_CONV_TWO=0|1|2 / DS_CONV_TWO_EARLY=0 = the two-channel-tile one-shot kernel: off | two tiles | every even
+ * count; waves 0-3 staging after the step's matrix instructions like waves 4-7; DS_DIRECT_VEC=0 = ds_conv2d_direct's
  * general kernel on whole 64-column tiles too.
  */
 #ifndef DIFFSCI_HIP_H

@@ -105,7 +105,7 @@ def _template_args(names, kernel):
 
 def test_volume_cases_reach_the_intended_kernels(tmp_path):
     """A numerical test of a route that was silently not taken proves nothing, and the library has no 'which kernel ran' query: the
-    driver's default arm under the profiler's kernel trace.  k_conv3p<PRE, CIRC, NRES, NPW, VEC, IMG> must appear with the fused loader
+    driver's default arm under the profiler's kernel trace.  k_conv3p<PRE, CIRC, NRES, VEC, IMG> must appear with the fused loader
     (f64, f128) and in its periodic variant (f64_circ), both with 16-byte patch loads; k_conv3h<MODE, W16, PRE, CIRC, NW, S16, IMGIN,
     TWO, VEC> in its 16x16x32 form with 16-byte loads (conv1 of the fused blocks, c64_128); k_convup (c256_128_up)."""
     prof = shutil.which("rocprofv3")
@@ -126,7 +126,7 @@ def test_volume_cases_reach_the_intended_kernels(tmp_path):
     p3 = _template_args(names, "k_conv3p")
     assert any(a[0] == "true" and a[1] == "false" for a in p3), "k_conv3p with the fused loader did not run:\n" + listing
     assert any(a[0] == "true" and a[1] == "true" for a in p3), "the periodic k_conv3p did not run:\n" + listing
-    assert all(a[4] == "true" and a[5] == "false" for a in p3), "k_conv3p without 16-byte loads, or on image input:\n" + listing
+    assert all(a[3] == "true" and a[4] == "false" for a in p3), "k_conv3p without 16-byte loads, or on image input:\n" + listing
     h3 = _template_args(names, "k_conv3h")
     assert h3, "k_conv3h did not run:\n" + listing
     assert any(a[0] == "0" and a[2] == "false" and a[5] == "true" and a[8] == "true" for a in h3), \

@@ -1,11 +1,15 @@
-// Diagnostic: where does a fp16x3 conv workgroup spend its life?  (s_memrealtime stamps, 100 MHz)
+// Diagnostic: where does a fp16x3 conv workgroup spend its life?  (s_memrealtime stamps, 100 MHz; the one-shot kernels of
+// ds_conv3h.hip: main() sets DS_CONV_PC=0, the persistent form has tools/conv3p_stamp.hip)
+//   hipcc --offload-arch=gfx950 -O3 -ffp-contract=off -std=c++17 -fno-slp-vectorize tools/conv3h_stamp.hip -o tools/bin/conv3h_stamp
 #define DS_STAMP 1
 #include "../diffsci_amd/csrc/ds_api.hip"
 #include "../diffsci_amd/csrc/ds_conv3h.hip"
+#include "../diffsci_amd/csrc/ds_conv3p.hip"
 #include <map>
 #include <vector>
 #include <algorithm>
 int main(int argc, char** argv) {
+  setenv("DS_CONV_PC", "0", 1);      // read once, by the first launch
   int B = argc > 1 ? atoi(argv[1]) : 64, Cin = argc > 2 ? atoi(argv[2]) : 64, Cout = Cin, S = argc > 3 ? atoi(argv[3]) : 128;
   const bool pre = argc > 4 && atoi(argv[4]) != 0;     // fused norm+SiLU loader and tile statistics
   size_t nin = (size_t)B * Cin * S * S, nout = (size_t)B * Cout * S * S;
@@ -32,7 +36,7 @@ int main(int argc, char** argv) {
   }
   hipMalloc(&g_stamps, (size_t)blocks * 16 * 8);
   const int reps = argc > 5 ? atoi(argv[5]) : 200;    // sustained launches: the clock settles under load
-  for (int it = 0; it < reps; ++it) ds_conv2d_h3(out, in, wp, 0, nullptr, nullptr, 0, nullptr, nullptr, B, Cin, Cout, S, S, 0, tab, stats, nullptr);
+  for (int it = 0; it < reps; ++it) ds_conv2d_h3(out, in, wp, 0, nullptr, nullptr, 0, nullptr, nullptr, B, Cin, Cout, S, S, 0, tab, stats, nullptr, nullptr, nullptr);
   hipDeviceSynchronize();
   std::vector<unsigned long long> h((size_t)blocks * 16);
   hipMemcpy(h.data(), g_stamps, h.size() * 8, hipMemcpyDeviceToHost);

@@ -14,7 +14,7 @@ ROOT = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(ROOT, "diffsci_amd", "csrc")
 OUTDIR = os.path.join(ROOT, "diffsci_amd", "_lib")
 LIB = os.path.join(OUTDIR, "libdiffsci_hip.so")
-SOURCES = ["ds_api.hip", "ds_step.hip", "ds_norm.hip", "ds_gnorm.hip", "ds_normtab.hip", "ds_conv.hip", "ds_conv6.hip", "ds_conv3h.hip", "ds_conv3p.hip", "ds_convup.hip", "ds_conv1h.hip", "ds_convdirect.hip", "ds_conv3d.hip", "ds_resample.hip", "ds_attn.hip", "ds_attn3h.hip", "ds_small.hip", "ds_amax.hip", "ds_tokens.hip", "ds_groupnorm.hip"]
+SOURCES = ["ds_api.hip", "ds_step.hip", "ds_norm.hip", "ds_gnorm.hip", "ds_normtab.hip", "ds_conv.hip", "ds_conv6.hip", "ds_conv3h.hip", "ds_conv3p.hip", "ds_convup.hip", "ds_conv1h.hip", "ds_conv_s2.hip", "ds_convdirect.hip", "ds_conv3d.hip", "ds_resample.hip", "ds_attn.hip", "ds_attn3h.hip", "ds_small.hip", "ds_amax.hip", "ds_tokens.hip", "ds_groupnorm.hip"]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 # -ffp-contract=off: the stepper / norm kernels reproduce the reference's one-rounding-per-op
 # arithmetic; MFMA kernels are unaffected (their FMAs are the matrix instruction's own).
@@ -24,7 +24,7 @@ FLAGS = ["--offload-arch=gfx950", "-O3", "-ffp-contract=off", "-fPIC", "-std=c++
 # which cannot carry the DPP modifier (two v_mov_b32_dpp + one packed add per step instead of two v_add_f32_dpp), and packed fp32
 # operations issue no faster than their two scalar halves on gfx950.  Same-box A/B: 77.4 -> 78.5 samples/s, launches 223.4 -> 219.3 us
 # (profiles/r02_noslp_ab.log); the attention kernel measured neutral with the flag and keeps the default.
-EXTRA_FLAGS = {f: ["-fno-slp-vectorize"] for f in ("ds_conv3h.hip", "ds_conv3p.hip", "ds_convup.hip", "ds_conv1h.hip")}
+EXTRA_FLAGS = {f: ["-fno-slp-vectorize"] for f in ("ds_conv3h.hip", "ds_conv3p.hip", "ds_convup.hip", "ds_conv1h.hip", "ds_conv_s2.hip")}
 # ds_conv3p.hip issues its LDS-DMA from inline assembly (the reason is in the file) and names m0, which that instruction reads, as
 # clobbered; clang warns that m0 is a reserved register.  No compiler-generated code of that kernel uses m0.
 EXTRA_FLAGS["ds_conv3p.hip"] = EXTRA_FLAGS["ds_conv3p.hip"] + ["-Wno-inline-asm"]

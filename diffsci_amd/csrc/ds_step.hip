@@ -91,15 +91,18 @@ __device__ __forceinline__ void box_muller(uint32_t a, uint32_t b, float& z0, fl
   z1 = rad * sn;
 }
 
-__device__ __forceinline__ float4 philox_normal4(const unsigned long long* __restrict__ state, unsigned long long offset,
-                                                 size_t i4) {
-  const unsigned long long seed = state[0], ctr = state[1] + offset + (unsigned long long)i4;
+__device__ __forceinline__ float4 philox_normal4_at(unsigned long long seed, unsigned long long ctr) {
   const uint4 r = philox4x32_10(make_uint4((uint32_t)ctr, (uint32_t)(ctr >> 32), 0u, 0u),
                                 make_uint2((uint32_t)seed, (uint32_t)(seed >> 32)));
   float4 z;
   box_muller(r.x, r.y, z.x, z.y);
   box_muller(r.z, r.w, z.z, z.w);
   return z;
+}
+
+__device__ __forceinline__ float4 philox_normal4(const unsigned long long* __restrict__ state, unsigned long long offset,
+                                                 size_t i4) {
+  return philox_normal4_at(state[0], state[1] + offset + (unsigned long long)i4);
 }
 
 __device__ __forceinline__ float philox_normal1(const unsigned long long* __restrict__ state, unsigned long long offset,
@@ -395,6 +398,40 @@ inline size_t vec4_count(size_t n, std::initializer_list<const void*> ptrs) {
 }
 inline int grid_elems(size_t n4, size_t n) { return grid_for(n4 ? n4 : (n + 3) / 4); }
 
+// VAENet.encode's posterior draw (vaenet.py:1244-1248): z = mean + exp(0.5 * logvar) * eps over moments [B, 2Z, S] (mean = the
+// first Z channels), a rounded product and a rounded sum as torch's; logvar clamped to [lo, hi] first when has_clamp.  A thread
+// takes four consecutive elements of z -- one Philox counter (element e <- counter base + e/4, output e%4: ds_philox_normal's
+// stream) -- and maps each to its sample on its own, so Z*S need not be a multiple of 4.  The stream's (seed, base) come from a
+// 16-byte device state when one is given (captured launches), else by value.
+template <bool PHILOX>
+__global__ __launch_bounds__(kThreads) void k_posterior(float* __restrict__ out, const float* __restrict__ moments,
+                                                        const float* __restrict__ eps, const unsigned long long* state,
+                                                        unsigned long long seed, unsigned long long offset, size_t per, size_t n,
+                                                        int has_clamp, float lo, float hi) {
+  const size_t n4 = (n + 3) / 4;
+  const size_t stride = (size_t)gridDim.x * kThreads;
+  for (size_t i = (size_t)blockIdx.x * kThreads + threadIdx.x; i < n4; i += stride) {
+    float z[4] = {0.f, 0.f, 0.f, 0.f};
+    if (PHILOX) {
+      float4 v;
+      v = state ? philox_normal4(state, offset, i) : philox_normal4_at(seed, offset + (unsigned long long)i);
+      z[0] = v.x; z[1] = v.y; z[2] = v.z; z[3] = v.w;
+    }
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const size_t e = 4 * i + j;
+      if (e < n) {
+        const size_t b = e / per, r = e - b * per;
+        const float mean = moments[2 * b * per + r];
+        float lv = moments[(2 * b + 1) * per + r];
+        if (has_clamp) lv = fminf(fmaxf(lv, lo), hi);
+        const float sd = expf(0.5f * lv);
+        out[e] = mean + sd * (PHILOX ? z[j] : eps[e]);
+      }
+    }
+  }
+}
+
 }  // namespace
 
 extern "C" {
@@ -590,6 +627,23 @@ int ds_add(float* out, const float* a, const float* b, size_t n, void* stream) {
   const size_t n4 = vec4_count(n, {out, a, b});
   hipLaunchKernelGGL(k_add, dim3(grid_elems(n4, n)), dim3(kThreads), 0, ds::as_stream(stream), out, a, b, n4, n);
   DS_CHECK_LAUNCH("ds_add");
+  return DS_OK;
+}
+
+int ds_posterior_sample(float* out, const float* moments, const float* eps, const uint64_t* philox_state, uint64_t philox_seed,
+                        uint64_t philox_offset, int B, size_t per, int has_clamp, float lo, float hi, void* stream) {
+  DS_REQUIRE(out && moments, DS_ERR_NULL, "ds_posterior_sample: NULL pointer");
+  DS_REQUIRE(!(eps && philox_state), DS_ERR_SHAPE, "ds_posterior_sample: give injected eps or a Philox state, not both");
+  DS_REQUIRE((reinterpret_cast<uintptr_t>(philox_state) & 7u) == 0, DS_ERR_SHAPE, "ds_posterior_sample: state must be 8-byte aligned");
+  DS_REQUIRE(B >= 0 && per > 0 && (!has_clamp || lo <= hi), DS_ERR_SHAPE, "ds_posterior_sample: bad arguments B=%d", B);
+  if (B == 0) return DS_OK;
+  const size_t n = (size_t)B * per;
+  dim3 g(grid_for((n + 3) / 4)), b(kThreads);
+  const unsigned long long* st = reinterpret_cast<const unsigned long long*>(philox_state);
+  if (eps) hipLaunchKernelGGL((k_posterior<false>), g, b, 0, ds::as_stream(stream), out, moments, eps, st, 0ull, 0ull, per, n, has_clamp, lo, hi);
+  else hipLaunchKernelGGL((k_posterior<true>), g, b, 0, ds::as_stream(stream), out, moments, eps, st, (unsigned long long)philox_seed,
+                          (unsigned long long)philox_offset, per, n, has_clamp, lo, hi);
+  DS_CHECK_LAUNCH("ds_posterior_sample");
   return DS_OK;
 }
 

@@ -9,3 +9,5 @@ from .autoencoders import LDMAutoencoderKLWrapper  # noqa: F401
 from . import autoencoderldm2d, autoencoderldm3d  # noqa: F401
 # the reference star-exports both modules, the 3-D one last: these names are the volume classes
 from .autoencoderldm3d import AttnBlock, AutoencoderKL, Decoder, ResnetBlock, Upsample, ddconfig  # noqa: F401
+from . import vaenet  # noqa: F401
+from .vaenet import VAENet, VAENetConfig  # noqa: F401

@@ -49,13 +49,14 @@ def set_ddconfig(cfg, given):
 
 
 class _Launcher(torch.nn.Module):
-    """What the blocks share: the dimension, the kernel switches and the packed weights (repacked when a weight, the device
-    or conv_precision changes)."""
+    """What the blocks share: the dimension, the kernel switches, the GroupNorm group count (32 in the LDM modules; VAENet's
+    blocks set their configuration's) and the packed weights (repacked when a weight, the device or conv_precision changes)."""
     _dim = 2
 
-    def _init_launcher(self):
+    def _init_launcher(self, num_groups=NUM_GROUPS):
         self.conv_precision = "fp16x3"
         self.fuse_norm = True
+        self.num_groups = num_groups
         self.__dict__["_packs"] = {}
 
     def _conv_cls(self):
@@ -121,13 +122,14 @@ class _Launcher(torch.nn.Module):
     def _norm_swish_conv(self, name, norm, conv, x, xs, res1=None, tile_stats=None):
         """conv(swish(norm(x))) [+ res1]; xs: the tile statistics x's producer left, or None."""
         count = x.numel() // (x.shape[0] * x.shape[1])
+        G = self.num_groups
         if self._folds():
-            tab = (ops.groupnorm_table(norm.weight, norm.bias, NUM_GROUPS, count, tile_stats=xs, eps=EPS) if xs is not None else
-                   ops.groupnorm_table(norm.weight, norm.bias, NUM_GROUPS, count, stats=ops.groupnorm_stats(x, NUM_GROUPS, EPS), eps=EPS))
+            tab = (ops.groupnorm_table(norm.weight, norm.bias, G, count, tile_stats=xs, eps=EPS) if xs is not None else
+                   ops.groupnorm_table(norm.weight, norm.bias, G, count, stats=ops.groupnorm_stats(x, G, EPS), eps=EPS))
             return self._conv3(name, conv, x, res1=res1, prenorm=tab, tile_stats=tile_stats)
-        st = ops.groupnorm_stats(x, NUM_GROUPS, EPS)
+        st = ops.groupnorm_stats(x, G, EPS)
         am = ops.amax_new(x.shape[0], x.device) if (self._dim == 2 and self.conv_precision == "fp16x3") else None
-        a = ops.groupnorm_apply(x, st, norm.weight, norm.bias, NUM_GROUPS, act=True, out_amax=am)
+        a = ops.groupnorm_apply(x, st, norm.weight, norm.bias, G, act=True, out_amax=am)
         return self._conv3(name, conv, a, res1=res1, in_amax=am)
 
 
@@ -201,13 +203,17 @@ class AttnBlock(_Launcher):
         B, C = x.shape[0], self.in_channels
         L = x.numel() // (B * C)
         h3 = self.conv_precision == "fp16x3"
-        st = (ops.groupnorm_stats_tiles(xs, NUM_GROUPS, L, EPS) if (xs is not None and self._folds())
-              else ops.groupnorm_stats(x, NUM_GROUPS, EPS))
+        G = self.num_groups
+        st = (ops.groupnorm_stats_tiles(xs, G, L, EPS) if (xs is not None and self._folds())
+              else ops.groupnorm_stats(x, G, EPS))
         a_in = ops.amax_new(B, x.device) if h3 else None
-        hn = ops.groupnorm_apply(x, st, self.norm.weight, self.norm.bias, NUM_GROUPS, act=False, out_amax=a_in)
-        a_qkv, a_o = (ops.amax_new(2 * B, x.device), ops.amax_new(B, x.device)) if h3 else (None, None)
+        hn = ops.groupnorm_apply(x, st, self.norm.weight, self.norm.bias, G, act=False, out_amax=a_in)
+        # one exponent for q and k, one for v, left by the in-projection where its split falls on a channel tile (2C % 64 == 0: every C
+        # that 32 groups divide; with fewer groups C may be 24, 48, ...: the attention then reduces q, k, v itself where it needs them)
+        split = 2 * C if (2 * C) % 64 == 0 else 0
+        a_qkv, a_o = (ops.amax_new(2 * B, x.device) if split else None, ops.amax_new(B, x.device)) if h3 else (None, None)
         qkv = self._conv1("qkv", (self.q.weight, self.k.weight, self.v.weight), (self.q.bias, self.k.bias, self.v.bias),
-                          self._v4(hn), in_amax=a_in, out_amax=a_qkv, amax_split=2 * C)          # one exponent for q and k, one for v
+                          self._v4(hn), in_amax=a_in, out_amax=a_qkv, amax_split=split)
         akw = dict(in_amax=a_qkv, out_amax=a_o) if h3 else {}
         o = ops.attention(qkv.view(B, 3 * C, L), C, precision=self.conv_precision, **akw)           # logits / sqrt(C)
         x4 = self._v4(x)

@@ -998,6 +998,168 @@ def conv_direct(x, w, bias=None, circular=False, out=None):
     return out
 
 
+# ---------------------------------------------------------------- stride-2 3x3(x3) convolution, zero pad at the far end (ds_conv_s2.hip)
+def _s2_sides(spatial, what):
+    if any(int(n) < 2 for n in spatial):
+        raise ValueError(f"{what}: the stride-2 convolution needs spatial sides of at least 2; got {tuple(int(n) for n in spatial)}")
+    return tuple(int(n) // 2 for n in spatial)
+
+
+def pack_conv_s2(w, precision="fp16x3"):
+    """A Downsample weight [Cout, Cin, 3, 3] for conv_s2: the fp16x3 packing (pack_conv's: the layout is the stride-1 kernel's)
+    at precision "fp16x3" when neither channel count is thin (> 4), else the raw weight (kind "direct") for the exact-fp32
+    kernel -- the routing of the stride-1 convolutions."""
+    require_device(w, "conv weight")
+    if precision not in CONV_PRECISIONS:
+        raise ValueError(f"unknown conv precision {precision!r}; choose from {CONV_PRECISIONS}")
+    if w.dim() != 4 or tuple(w.shape[2:]) != (3, 3):
+        raise ValueError(f"pack_conv_s2: weight must be [Cout, Cin, 3, 3]; got {tuple(w.shape)}")
+    if precision == "fp16x3" and min(w.shape[0], w.shape[1]) > 4:
+        return pack_conv(w, "fp16x3")
+    return PackedConv(w.detach().contiguous().clone(), w.shape[0], w.shape[1], 3, "direct")
+
+
+def conv_s2(x, pw, bias=None, res1=None, in_amax=None, out_amax=None, out=None):
+    """out[b,co,i,j] = bias[co] + sum w[co,ci,ky,kx] x[b,ci,2i+ky,2j+kx] (+ res1), x = 0 past the far edge: F.conv2d(F.pad(x,
+    (0,1,0,1)), w, b, stride=2); x [B, Cin, H, W] with H, W >= 2 -> [B, Cout, H//2, W//2].  pw = pack_conv_s2(w, precision).
+    fp16x3 form: in_amax / out_amax as conv2d's.  No tile statistics are produced."""
+    require_device(x, "x")
+    if x.dim() != 4 or x.shape[1] != pw.Cin or pw.ks != 3:
+        raise ValueError(f"conv_s2: x must be [B, {pw.Cin}, H, W] and the weight 3x3; got {tuple(x.shape)}")
+    B, Cin, Hin, Win = x.shape
+    H, W = _s2_sides((Hin, Win), "conv_s2")
+    if out is None:
+        out = torch.empty((B, pw.Cout, H, W), dtype=torch.float32, device=x.device)
+    elif tuple(out.shape) != (B, pw.Cout, H, W):
+        raise ValueError(f"out has shape {tuple(out.shape)}, expected {(B, pw.Cout, H, W)}")
+    if res1 is not None and tuple(res1.shape) != tuple(out.shape):
+        raise ValueError("residual shape mismatch")
+    if bias is not None and bias.numel() != pw.Cout:
+        raise ValueError("bias must have Cout entries")
+    x = x.contiguous()
+    if pw.kind == "fp16x3":
+        pin = _in_amax(x, in_amax, B, raw=True)
+        N.check(N.lib().ds_conv2d_s2_h3(_p(out, "out"), _p(x), _p(pw.data), int(pw.wshift), _p(bias), _p(res1), B, Cin, pw.Cout, Hin, Win,
+                                        1, 1, 0, pin, _pi(out_amax, B, "out_amax"), _stream()), "ds_conv2d_s2_h3")
+    elif pw.kind == "direct":
+        N.check(N.lib().ds_conv2d_s2_direct(_p(out, "out"), _p(x), _p(pw.data), _p(bias), _p(res1), B, Cin, pw.Cout, Hin, Win, _stream()),
+                "ds_conv2d_s2_direct")
+        if out_amax is not None:
+            absmax_rows(out, out=out_amax)
+    else:
+        raise ValueError(f"conv_s2: packing of kind {pw.kind!r}; use pack_conv_s2")
+    return out
+
+
+def pack_conv3d_s2(w, precision="fp16x3"):
+    """A Downsample weight [Cout, Cin, 3, 3, 3] for conv3d_s2: three fp16x3 packings, one per depth tap, or the raw weight
+    (thin layers, other precisions: the exact-fp32 direct kernel)."""
+    require_device(w, "conv weight")
+    if precision not in CONV_PRECISIONS:
+        raise ValueError(f"unknown conv precision {precision!r}; choose from {CONV_PRECISIONS}")
+    if w.dim() != 5 or tuple(w.shape[2:]) != (3, 3, 3):
+        raise ValueError(f"pack_conv3d_s2: weight must be [Cout, Cin, 3, 3, 3]; got {tuple(w.shape)}")
+    if precision == "fp16x3" and min(w.shape[0], w.shape[1]) > 4:
+        return [pack_conv(w[:, :, kz].contiguous(), "fp16x3") for kz in range(3)]
+    return PackedConv(w.detach().contiguous().clone(), w.shape[0], w.shape[1], 3, "direct")
+
+
+def conv3d_s2(x, packs, bias=None, res1=None, out=None, ws=None):
+    """The same on a volume [B, Cin, D, H, W] (sides >= 2) -> [B, Cout, D//2, H//2, W//2]: F.conv3d(F.pad(x, (0,1)*3), w, b,
+    stride=2).  packs = pack_conv3d_s2(w, precision).  Matrix-core form, composed as conv3d_mfma: one slice-major copy with a zero
+    slice past either end (ds_volume_to_slices), then one 2-D stride-2 launch per depth tap over the batch of OUTPUT slices --
+    output slice d of a sample reads its slices 2d + kz, which the launch addresses by a sample stride of two slices, so there is
+    no gather pass -- accumulated in place, and the slice -> volume copy (which adds res1).  ws: buffer pool, as conv3d_mfma's."""
+    require_device(x, "x")
+    direct = isinstance(packs, PackedConv)
+    Cin, Cout = (packs.Cin, packs.Cout) if direct else (packs[0].Cin, packs[0].Cout)
+    if x.dim() != 5 or x.shape[1] != Cin:
+        raise ValueError(f"conv3d_s2: x must be [B, {Cin}, D, H, W]; got {tuple(x.shape)}")
+    B, _, Din, Hin, Win = x.shape
+    D, H, W = _s2_sides((Din, Hin, Win), "conv3d_s2")
+    if out is None:
+        out = torch.empty((B, Cout, D, H, W), dtype=torch.float32, device=x.device)
+    elif tuple(out.shape) != (B, Cout, D, H, W):
+        raise ValueError(f"out has shape {tuple(out.shape)}, expected {(B, Cout, D, H, W)}")
+    if res1 is not None and tuple(res1.shape) != tuple(out.shape):
+        raise ValueError("residual shape mismatch")
+    if bias is not None and bias.numel() != Cout:
+        raise ValueError("bias must have Cout entries")
+    x = x.contiguous()
+    if direct:
+        if packs.kind != "direct":
+            raise ValueError("conv3d_s2: use pack_conv3d_s2")
+        N.check(N.lib().ds_conv3d_s2_direct(_p(out, "out"), _p(x), _p(packs.data), _p(bias), _p(res1), B, Cin, Cout, Din, Hin, Win,
+                                            _stream()), "ds_conv3d_s2_direct")
+        return out
+
+    def take(shape):
+        return torch.empty(shape, dtype=torch.float32, device=x.device) if ws is None else ws.take(shape, x.device)
+    ns = B * (Din + 2)
+    s_in = take((ns, Cin, Hin, Win))
+    N.check(N.lib().ds_volume_to_slices(_p(s_in), _p(x), B, Cin, Din, Hin * Win, 0, 0, 1, _stream()), "ds_volume_to_slices")
+    if ws is None:
+        am = absmax_rows(s_in)
+        am_buf = None
+    else:
+        am_buf = ws.take((ns,), x.device)
+        am = absmax_rows(s_in, out=amax_zero(am_buf.view(torch.int32)))
+    s_out = take((B * D, Cout, H, W))
+    for kz in range(3):                                  # slice 1 + 2d + kz of the sample's D + 2
+        pk = packs[kz]
+        N.check(N.lib().ds_conv2d_s2_h3(_p(s_out), s_in[1 + kz].data_ptr(), _p(pk.data), int(pk.wshift), _p(bias) if kz == 0 else None,
+                                        None if kz == 0 else _p(s_out), B * D, Cin, Cout, Hin, Win, D, Din + 2, 2,
+                                        am.data_ptr() + 4 * (1 + kz), None, _stream()), "ds_conv2d_s2_h3")
+    _from_slices(out, s_out, res1, None, B, Cout, D, H * W, pad=0)
+    if ws is not None:
+        for t in (s_in, s_out, am_buf):
+            if t is not None:
+                ws.give(t)
+    return out
+
+
+def posterior_sample(moments, eps=None, clamp=None, out=None):
+    """z = mean + exp(0.5 logvar) eps for moments [B, 2Z, *spatial] = (mean | logvar) -> [B, Z, *spatial]: the draw of
+    VAENet.encode (vaenet.py:1244-1248).  clamp = (lo, hi) clamps logvar first (the reference's DiagonalGaussianDistribution uses
+    (-30, 20); VAENet none).  eps given: read.  eps=None: drawn inside the kernel by the steppers' Philox stream, seeded from
+    torch's CUDA generator -- reproducible from torch.manual_seed, and the generator advances by what the draw consumes.  Under
+    stream capture the 16-byte (seed, offset) state is itself drawn on the device from that generator (host code cannot read
+    it while capturing), so every replay draws fresh noise."""
+    require_device(moments, "moments")
+    if moments.dim() < 3 or moments.shape[1] % 2:
+        raise ValueError(f"posterior_sample: moments must be [B, 2Z, *spatial]; got {tuple(moments.shape)}")
+    moments = moments.contiguous()
+    B, Z = moments.shape[0], moments.shape[1] // 2
+    shape = (B, Z) + tuple(moments.shape[2:])
+    per = moments.numel() // max(2 * B, 1)
+    if out is None:
+        out = torch.empty(shape, dtype=torch.float32, device=moments.device)
+    elif tuple(out.shape) != shape:
+        raise ValueError(f"out has shape {tuple(out.shape)}, expected {shape}")
+    lo, hi, has = 0.0, 0.0, 0
+    if clamp is not None:
+        lo, hi = (float(v) for v in clamp)
+        if not lo <= hi:
+            raise ValueError(f"posterior_sample: clamp {clamp!r}")
+        has = 1
+    if per == 0 or B == 0:
+        return out
+    state, seed, offset = None, 0, 0
+    if eps is not None:
+        if tuple(eps.shape) != shape:
+            raise ValueError(f"eps has shape {tuple(eps.shape)}, expected {shape}")
+        eps = eps.contiguous()
+    elif torch.cuda.is_current_stream_capturing():
+        state = torch.randint(0, 1 << 62, (2,), dtype=torch.int64, device=moments.device)
+    else:
+        gen = torch.cuda.default_generators[moments.device.index]
+        seed, offset = int(gen.initial_seed()), int(gen.get_offset())
+        gen.set_offset(offset + (philox_counters(B * per) + 3) // 4 * 4)          # torch keeps its offset a multiple of 4
+    N.check(N.lib().ds_posterior_sample(_p(out, "out"), _p(moments), _p(eps, "eps"), None if state is None else state.data_ptr(),
+                                        seed & ((1 << 64) - 1), offset, B, per, has, lo, hi, _stream()), "ds_posterior_sample")
+    return out
+
+
 def conv_tile_count(H, W):
     """Pixel tiles per channel plane in the fp16x3 kernels' tile_stats layout."""
     return N.lib().ds_conv_tile_count(int(H), int(W))

@@ -626,6 +626,33 @@ int ds_patch_unembed(float* y, const float* x, const float* w, const float* bias
                      void* stream);
 
 /* ------------------------------------------------------------------------------------
+ * VAENet first stage (vaenet.py): the encoder's Downsample and the posterior draw.
+ * ---------------------------------------------------------------------------------- */
+/* Stride-2 3x3 convolution, zero padding at the far end only (Downsample.forward with a convolution, vaenet.py:662-673):
+ *   out[b,co,i,j] = bias[co] + sum w[co,ci,ky,kx] * in[b,ci,2i+ky,2j+kx] (+ res1),  in = 0 where an index reaches Hin / Win;
+ * out is [B, Cout, Hin/2, Win/2] (floor) and Hin, Win >= 2.
+ *   ds_conv2d_s2_h3: the fp16x3 matrix-core form; w_packed / wshift from ds_conv2d_h3_pack_weights; in_amax / out_amax as
+ *     ds_conv2d_h3's (in_amax indexed by the INPUT sample).  Output sample n reads input sample (n / nin) * so + (n % nin) * si:
+ *     (nin = 1, so = 1, si = 0) is the identity; the depth taps of a stride-2 volume convolution run it over a slice-major copy
+ *     with (nin = Dout, so = D + 2, si = 2) and in advanced by (1 + kz) slices, accumulating through res1 = out.
+ *   ds_conv2d_s2_direct / ds_conv3d_s2_direct: exact fp32 (fmaf chains, channels outer, taps inner), torch weight layout
+ *     [Cout,Cin,3,3] / [Cout,Cin,3,3,3]: thin layers and the non-fp16x3 precisions. */
+int ds_conv2d_s2_h3(float* out, const float* in, const void* w_packed, int wshift, const float* bias, const float* res1, int B,
+                    int Cin, int Cout, int Hin, int Win, int nin, int so, int si, const unsigned* in_amax, unsigned* out_amax,
+                    void* stream);
+int ds_conv2d_s2_direct(float* out, const float* in, const float* w, const float* bias, const float* res1, int B, int Cin, int Cout,
+                        int Hin, int Win, void* stream);
+int ds_conv3d_s2_direct(float* out, const float* in, const float* w, const float* bias, const float* res1, int B, int Cin, int Cout,
+                        int Din, int Hin, int Win, void* stream);
+
+/* VAENet.encode's draw (vaenet.py:1244-1248): moments [B, 2Z, S] -> out [B, Z, S] = mean + exp(0.5 * logvar) * eps, per = Z*S;
+ * has_clamp: logvar is clamped to [lo, hi] first.  eps != NULL: read ([B, Z, S]); else generated in the kernel, element e of out
+ * from Philox counter base + e/4 (ds_philox_normal's stream) with (seed, base) = (philox_state[0], philox_state[1] +
+ * philox_offset) when philox_state != NULL (device memory: captured launches), else (philox_seed, philox_offset) by value. */
+int ds_posterior_sample(float* out, const float* moments, const float* eps, const uint64_t* philox_state, uint64_t philox_seed,
+                        uint64_t philox_offset, int B, size_t per, int has_clamp, float lo, float hi, void* stream);
+
+/* ------------------------------------------------------------------------------------
  * hipGraph capture of a launch sequence (the whole N-step loop is captured once per
  * (network, nsteps, batch) and replayed).
  * ---------------------------------------------------------------------------------- */

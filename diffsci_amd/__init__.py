@@ -7,5 +7,6 @@ hand-written HIP kernels (libdiffsci_hip.so, include/diffsci_hip.h); there is no
 """
 from . import _native, ops  # noqa: F401
 from . import models  # noqa: F401
+from . import extra  # noqa: F401
 
 __version__ = "0.1.0"

@@ -132,6 +132,8 @@ _PROTOS = {
     "ds_conv2d_s2_direct": (c_int, [_P, _P, _P, _P, _P, c_int, c_int, c_int, c_int, c_int, _P]),
     "ds_conv3d_s2_direct": (c_int, [_P, _P, _P, _P, _P, c_int, c_int, c_int, c_int, c_int, c_int, _P]),
     "ds_posterior_sample": (c_int, [_P, _P, _P, _P, c_uint64, c_uint64, c_int, c_size_t, c_int, c_float, c_float, _P]),
+    "ds_box_copy3d": (c_int, [_P, _P, c_int, c_int, c_int, c_int, c_longlong, c_longlong, c_longlong, c_int, c_int, c_int,
+                              c_int, c_int, c_int, c_int, c_int, c_int, _P]),
     "ds_graph_begin_capture": (c_int, [_P]),
     "ds_graph_end_capture": (c_int, [_P, POINTER(_P), POINTER(c_int)]),
     "ds_graph_launch": (c_int, [_P, _P]),

@@ -315,38 +315,57 @@ class Decoder(_Launcher):
             if isinstance(m, _Launcher) and m is not self:
                 m.conv_precision, m.fuse_norm = self.conv_precision, self.fuse_norm
 
-    @ops.device_guard
-    def forward(self, z):
-        if self.training and self.dropout > 0:
-            raise NotImplementedError("dropout > 0 in training mode is outside the HIP sampling path: call .eval()")
-        z = self._check(z, self.z_channels, "Decoder")
-        self._hand_down()
+    # The walk in the three pieces a tiled decode runs one at a time (diffsci_amd/extra/chunk_decode.py); each takes and returns
+    # (h, hs): the activation and the tile statistics its producer left (None off the folded route: always on volumes).
+    @staticmethod
+    def _attend(att, h, hs):
+        return att._run(h, hs) if isinstance(att, AttnBlock) else (h, hs)          # Identity for attn_type "none"
+
+    def _stage0(self, z):
+        """conv_in, mid.block_1, mid.attn_1 if present, mid.block_2."""
         self.last_z_shape = z.shape
-        B, dev = z.shape[0], z.device
-
-        def attend(att, h, hs):
-            return att._run(h, hs) if isinstance(att, AttnBlock) else (h, hs)          # Identity for attn_type "none"
-
-        hs = self._tiles(B, self.conv_in.out_channels, z.shape[2:], dev)
+        hs = self._tiles(z.shape[0], self.conv_in.out_channels, z.shape[2:], z.device)
         h = self._conv3("conv_in", self.conv_in, z, tile_stats=hs)
         h, hs = self.mid.block_1._run(h, hs)
         if self.has_mid_attn:
-            h, hs = attend(self.mid.attn_1, h, hs)
-        h, hs = self.mid.block_2._run(h, hs)
-        for i_level in reversed(range(self.num_resolutions)):
-            up = self.up[i_level]
-            for i_block in range(self.num_res_blocks + 1):
-                h, hs = up.block[i_block]._run(h, hs)
-                if len(up.attn) > 0:
-                    h, hs = attend(up.attn[i_block], h, hs)
-            if i_level != 0:
-                h, hs = up.upsample._run(h, hs)
+            h, hs = self._attend(self.mid.attn_1, h, hs)
+        return self.mid.block_2._run(h, hs)
+
+    def _level_blocks(self, i_level, h, hs):
+        up = self.up[i_level]
+        for i_block in range(self.num_res_blocks + 1):
+            h, hs = up.block[i_block]._run(h, hs)
+            if len(up.attn) > 0:
+                h, hs = self._attend(up.attn[i_block], h, hs)
+        return h, hs
+
+    def _up_stage(self, i_level, h, hs=None):
+        """up[i_level]'s blocks and attention, then its upsample (i_level >= 1)."""
+        h, hs = self._level_blocks(i_level, h, hs)
+        return self.up[i_level].upsample._run(h, hs)
+
+    def _final_stage(self, h, hs=None):
+        """up[0]'s blocks, then norm_out + swish + conv_out and tanh if configured."""
+        h, hs = self._level_blocks(0, h, hs)
         if self.give_pre_end:
             return h
         h = self._norm_swish_conv("conv_out", self.norm_out, self.conv_out, h, hs)
         if self.tanh_out:
             h = ops.tanh(h)
         return h
+
+    def _walk(self, z):
+        self._hand_down()
+        h, hs = self._stage0(z)
+        for i_level in reversed(range(1, self.num_resolutions)):
+            h, hs = self._up_stage(i_level, h, hs)
+        return self._final_stage(h, hs)
+
+    @ops.device_guard
+    def forward(self, z):
+        if self.training and self.dropout > 0:
+            raise NotImplementedError("dropout > 0 in training mode is outside the HIP sampling path: call .eval()")
+        return self._walk(self._check(z, self.z_channels, "Decoder"))
 
 
 class AutoencoderKL(_Launcher):

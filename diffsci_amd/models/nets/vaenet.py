@@ -17,8 +17,9 @@ the nearest-x2 loader) with the configuration's ``num_groups``; what is new here
 
 ``patch_size`` is accepted and ignored (patching changes the reference's memory use, not its values); ``use_flash_attention``
 selects between two formulations of the same softmax attention there and nothing here.  Not built: dimension=1, time
-embeddings, minimal_rf_mode, linear attention (NotImplementedError at construction), the receptive-field calculators and the
-chunked decode."""
+embeddings, minimal_rf_mode, linear attention (NotImplementedError at construction).  ``calculate_receptive_field`` of the
+encoder, the decoder and the net return the reference's dicts; the chunked volume decode that reads them is
+diffsci_amd/extra/chunk_decode.py."""
 import pathlib
 from typing import List
 
@@ -314,6 +315,50 @@ def _hand_down(root):
             m.conv_precision, m.fuse_norm = root.conv_precision, root.fuse_norm
 
 
+def _has_attention(config):
+    """An attention block sees the whole volume; attn_type "none" builds Identity in its place."""
+    return config.attn_type != "none" and bool(config.has_mid_attn or len(config.attn_resolutions) > 0)
+
+
+def _rf_per_block(config):
+    return 2 if getattr(config, "minimal_rf_mode", False) else 4          # two 3x3 convolutions, or MinimalResnetBlock's one
+
+
+def _rf_mode(config):
+    return "minimal" if getattr(config, "minimal_rf_mode", False) else "standard"
+
+
+def _grow(trace, rf, by, what):
+    trace.append(f"{what}: RF = {rf + by}")
+    return rf + by
+
+
+def decoder_receptive_field(cfg):
+    """vaenet.py:1142-1228: the receptive field in latent cells after every piece of the walk -- what a tiled decode sizes
+    its halos from (extra/chunk_decode.py) -- or the infinite case when an attention block is configured."""
+    if _has_attention(cfg):
+        return {"rf_latent": float("inf"), "has_attention": True, "feasible_chunking": False,
+                "reason": "Decoder uses global attention"}
+    per_block = _rf_per_block(cfg)
+    trace = ["post_quant_conv (1x1): RF = 1"]
+    rf = _grow(trace, 1, 2, "conv_in (3x3)")
+    rf = _grow(trace, rf, per_block, "mid.block_1")
+    rf = rf_mid = _grow(trace, rf, per_block, "mid.block_2")
+    blocks = cfg.num_res_blocks + 1
+    for i_level in reversed(range(cfg.num_resolutions)):
+        rf = _grow(trace, rf, blocks * per_block, f"up[{i_level}] ({blocks} blocks)")
+        if i_level != 0:
+            trace.append(f"up[{i_level}].upsample (no RF change in latent coords)")
+    rf = _grow(trace, rf, 2, "conv_out (3x3)")
+    overlap = int(rf * 1.5)                       # the reference's suggestion: 1.5 rf, up to 16 / 24 / 32 / a multiple of 16
+    overlap = next((n for n in (16, 24, 32) if overlap <= n), -(-overlap // 16) * 16)
+    factor = 2 ** (cfg.num_resolutions - 1)
+    return {"rf_latent": rf, "rf_after_middle": rf_mid, "rf_output": rf * factor, "min_overlap": rf,
+            "recommended_overlap": overlap, "spatial_upsampling_factor": factor, "has_attention": False,
+            "feasible_chunking": True, "trace": trace, "rf_per_block": per_block, "mode": _rf_mode(cfg),
+            "num_convolutions": sum("RF" in t and "no RF" not in t for t in trace)}
+
+
 class VAEEncoder(_Launcher):
     """vaenet.py:685-876.  conv_precision / fuse_norm are read at every forward and handed down, as on the LDM Decoder."""
 
@@ -387,6 +432,26 @@ class VAEEncoder(_Launcher):
         m = self.quant_conv
         return self._conv1("quant_conv", (m.weight,), (m.bias,), self._v4(h)).view((B, m.out_channels) + tuple(h.shape[2:]))
 
+    def calculate_receptive_field(self):
+        """vaenet.py:878-945: the receptive field in input cells (3x3 convolutions add 2, a block 4, a strided convolution 2, a
+        pooling 1, each counted at full resolution as the reference does), and that over the downsampling factor."""
+        cfg = self.config
+        if _has_attention(cfg):
+            return {"rf_input": float("inf"), "rf_latent": float("inf"), "has_attention": True, "feasible_chunking": False}
+        per_block = _rf_per_block(cfg)
+        trace = []
+        rf = _grow(trace, 1, 2, "conv_in")
+        stride = 1
+        for i_level in range(cfg.num_resolutions):
+            rf = _grow(trace, rf, cfg.num_res_blocks * per_block, f"down[{i_level}] ({cfg.num_res_blocks} blocks)")
+            if i_level != cfg.num_resolutions - 1:
+                rf = _grow(trace, rf, 2 if cfg.resamp_with_conv else 1, f"down[{i_level}].downsample")
+                stride *= 2
+        rf = _grow(trace, rf, 2 * per_block, "mid blocks")
+        rf = _grow(trace, rf, 2, "conv_out")
+        return {"rf_input": rf, "rf_latent": rf // stride, "downsampling_factor": stride, "has_attention": False,
+                "feasible_chunking": True, "trace": trace, "rf_per_block": per_block, "mode": _rf_mode(cfg)}
+
 
 class VAEDecoder(L.Decoder):
     """vaenet.py:948-1140: post_quant_conv, then the LDM decoder's walk.  memory_efficient_variant only changes the channel
@@ -442,15 +507,21 @@ class VAEDecoder(L.Decoder):
                              num_res_blocks=config.num_res_blocks, give_pre_end=False, tanh_out=config.tanh_out)
         self._init_launcher(config.num_groups)
 
+    def _stage0(self, z):
+        """post_quant_conv, then the LDM decoder's stage 0."""
+        m = self.post_quant_conv
+        h = self._conv1("post_quant_conv", (m.weight,), (m.bias,), self._v4(z))
+        return L.Decoder._stage0(self, h.view((z.shape[0], m.out_channels) + tuple(z.shape[2:])))
+
     @ops.device_guard
     def forward(self, z, time=None):
         _refuse_time(time)
         if self.training and self.config.dropout > 0:
             raise NotImplementedError("dropout > 0 in training mode is outside the HIP sampling path: call .eval()")
-        z = self._check(z, self.config.z_dim, "VAEDecoder")
-        m = self.post_quant_conv
-        h = self._conv1("post_quant_conv", (m.weight,), (m.bias,), self._v4(z))
-        return L.Decoder.forward(self, h.view((z.shape[0], m.out_channels) + tuple(z.shape[2:])))
+        return self._walk(self._check(z, self.config.z_dim, "VAEDecoder"))
+
+    def calculate_receptive_field(self):
+        return decoder_receptive_field(self.config)
 
 
 class VAENet(torch.nn.Module):
@@ -489,3 +560,30 @@ class VAENet(torch.nn.Module):
 
     def export_description(self) -> dict:
         return {"config": self.config.export_description()}
+
+    def calculate_receptive_field(self):
+        """vaenet.py:1267-1286: both halves' fields and the configuration entries they follow from."""
+        cfg = self.config
+        return {"encoder": self.encoder.calculate_receptive_field(), "decoder": self.decoder.calculate_receptive_field(),
+                "config": {"minimal_rf_mode": getattr(cfg, "minimal_rf_mode", False), "num_res_blocks": cfg.num_res_blocks,
+                           "ch_mult": cfg.ch_mult, "has_mid_attn": cfg.has_mid_attn, "attn_type": cfg.attn_type,
+                           "attn_resolutions": cfg.attn_resolutions}}
+
+    def print_receptive_field_summary(self):
+        """calculate_receptive_field() as text."""
+        info, cfg = self.calculate_receptive_field(), self.config
+        enc, dec = info["encoder"], info["decoder"]
+        print(f"VAENet receptive fields ({cfg.dimension}-D, ch_mult {cfg.ch_mult}, num_res_blocks {cfg.num_res_blocks}, "
+              f"has_mid_attn {cfg.has_mid_attn}, attn_type {cfg.attn_type!r}, {_rf_mode(cfg)} blocks)")
+        if enc["has_attention"]:
+            print("  encoder: global attention, the field is unbounded")
+        else:
+            print(f"  encoder: {enc['rf_input']} input cells = {enc['rf_latent']} latent cells "
+                  f"(downsampling x{enc['downsampling_factor']})")
+        if dec["has_attention"]:
+            print("  decoder: global attention, the field is unbounded: a chunked decode is not feasible")
+        else:
+            print(f"  decoder: {dec['rf_latent']} latent cells ({dec['rf_after_middle']} after the middle blocks) = "
+                  f"{dec['rf_output']} output cells (upsampling x{dec['spatial_upsampling_factor']})")
+            print(f"  chunked decode: feasible; overlap at least {dec['min_overlap']} latent cells, suggested "
+                  f"{dec['recommended_overlap']}")

@@ -1160,6 +1160,46 @@ def posterior_sample(moments, eps=None, clamp=None, out=None):
     return out
 
 
+def _triple(v, what):
+    if not isinstance(v, (tuple, list, torch.Size)) or len(v) != 3:
+        raise ValueError(f"box_copy3d: {what} must be three integers; got {v!r}")
+    return tuple(int(a) for a in v)
+
+
+def box_copy3d(src, src_start, dst, dst_start, size):
+    """dst[..., d0+i, d1+j, d2+k] = src[..., (s0+i) % S0, (s1+j) % S1, (s2+k) % S2] for 0 <= (i, j, k) < size, plane by plane
+    (ds_window.hip).  src and dst: contiguous fp32 tensors whose last three axes are the box's and whose leading axes hold the
+    same number of planes.  The source is periodic -- a start may be negative and a box longer than the axis -- the destination
+    box must lie inside dst.  ValueError before any launch: a non-fp32 tensor, different plane counts, a destination box
+    outside dst, src and dst sharing storage.  An empty box launches nothing.  Returns dst."""
+    for t, what in ((src, "src"), (dst, "dst")):
+        if not isinstance(t, torch.Tensor):
+            raise TypeError(f"box_copy3d: {what} must be a torch.Tensor")
+        if t.dtype != torch.float32:
+            raise ValueError(f"box_copy3d: {what} has dtype {t.dtype}; the copy is fp32 only")
+        if t.dim() < 3:
+            raise ValueError(f"box_copy3d: {what} needs at least three axes; got {tuple(t.shape)}")
+    s, d, L = _triple(src_start, "src_start"), _triple(dst_start, "dst_start"), _triple(size, "size")
+    S, D = tuple(src.shape[-3:]), tuple(dst.shape[-3:])
+    planes = src.numel() // max(S[0] * S[1] * S[2], 1)
+    if min(S) < 1 or min(D) < 1:
+        raise ValueError(f"box_copy3d: empty spatial axes (src {S}, dst {D})")
+    if planes != dst.numel() // (D[0] * D[1] * D[2]):
+        raise ValueError(f"box_copy3d: src {tuple(src.shape)} and dst {tuple(dst.shape)} hold different numbers of planes")
+    if min(L) < 0 or any(a < 0 or a + n > m for a, n, m in zip(d, L, D)):
+        raise ValueError(f"box_copy3d: destination box start {d} size {L} leaves dst {D}")
+    if src.untyped_storage().data_ptr() == dst.untyped_storage().data_ptr() and src.numel() and dst.numel():
+        raise ValueError("box_copy3d: src and dst share storage")
+    if max(S + D) >= 1 << 31 or L[0] * L[1] >= (1 << 31) - (1 << 20) or planes >= 1 << 31:
+        raise ValueError(f"box_copy3d: axes beyond 31 bits (src {S}, dst {D}, box {L})")
+    ps, pd = _p(src, "src"), _p(dst, "dst")
+    if planes == 0 or min(L) == 0:
+        return dst
+    N.check(N.lib().ds_box_copy3d(pd, ps, planes, S[0], S[1], S[2], s[0], s[1], s[2], D[0], D[1], D[2], d[0], d[1], d[2],
+                                  L[0], L[1], L[2], _stream()), "ds_box_copy3d")
+    return dst
+
+
 def conv_tile_count(H, W):
     """Pixel tiles per channel plane in the fp16x3 kernels' tile_stats layout."""
     return N.lib().ds_conv_tile_count(int(H), int(W))

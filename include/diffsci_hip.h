@@ -652,6 +652,14 @@ int ds_conv3d_s2_direct(float* out, const float* in, const float* w, const float
 int ds_posterior_sample(float* out, const float* moments, const float* eps, const uint64_t* philox_state, uint64_t philox_seed,
                         uint64_t philox_offset, int B, size_t per, int has_clamp, float lo, float hi, void* stream);
 
+/* Box copy with a periodic source (the halo gather and centre scatter of the chunked volume decode), fp32:
+ *   dst[n, d0+i, d1+j, d2+k] = src[n, (s0+i) mod S0, (s1+j) mod S1, (s2+k) mod S2]    0 <= i < L0, j < L1, k < L2, n < planes
+ * src [planes, S0, S1, S2], dst [planes, D0, D1, D2], both dense.  The modulus is Euclidean: a source start may be negative and a
+ * box may span several periods of an axis.  The destination box must lie inside dst (DS_ERR_SHAPE otherwise: nothing is
+ * launched); src and dst must not overlap.  An empty box launches nothing.  Element offsets are 64-bit; L0 * L1 < 2^31. */
+int ds_box_copy3d(float* dst, const float* src, int planes, int S0, int S1, int S2, long long s0, long long s1, long long s2, int D0,
+                  int D1, int D2, int d0, int d1, int d2, int L0, int L1, int L2, void* stream);
+
 /* ------------------------------------------------------------------------------------
  * hipGraph capture of a launch sequence (the whole N-step loop is captured once per
  * (network, nsteps, batch) and replayed).

@@ -15,6 +15,7 @@ import torch
 from ... import ops
 from ..._native import DS_IN_NETWORK, DS_IN_SCORE
 from ..nets import precision
+from ..nets.runtime import tensor_version
 from .steptable import StepTable
 
 
@@ -114,7 +115,7 @@ def model_signature(model):
     out = []
     for d, name in slots[2]:
         p = d[name]
-        out.append((p.data_ptr(), p._version) if p is not None else None)
+        out.append((p.data_ptr(), tensor_version(p)) if p is not None else None)
     return tuple(out), tuple(getattr(model, a, None) for a in MODEL_SWITCHES)
 
 

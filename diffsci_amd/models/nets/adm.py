@@ -26,7 +26,9 @@ import yaml
 from ... import ops
 from ..._native import DS_LOAD_AVGPOOL2, DS_LOAD_PLAIN, DS_LOAD_UPSAMPLE2
 from . import precision
-from .punetg import _AffineHolder, _AmaxArena, _Attn, _CircConv, _Fourier, _Workspace, make_conv, require_eval
+from . import runtime
+from .punetg import _AffineHolder, _Attn, _CircConv, _Fourier, make_conv
+from .runtime import AmaxArena, Workspace, require_eval, shift_rows, weights_signature
 
 _FIELDS = dict(
     input_channels=1, output_channels=1, dimension=2, model_channels=64, time_embed_dim=64,
@@ -220,7 +222,7 @@ class ADMBaseBlock(torch.nn.Module):
     def _packs(self):
         convs = [self.conv1, self.conv2] + ([self.convresidual] if self.has_residual else [])
         tracked = [m.weight for m in convs] + ([self.attn.mhattn.in_proj_weight, self.attn.mhattn.out_proj.weight] if self.has_attn else [])
-        sig = (self.conv_precision,) + tuple((t.data_ptr(), t._version) for t in tracked)
+        sig = weights_signature(tracked, self.conv_precision)
         if self._packed is not None and sig == self._packed_sig:
             return self._packed
         pk = {}
@@ -655,7 +657,7 @@ class ADM(torch.nn.Module):
         self.tile_stats_norms = os.environ.get("DIFFSCI_TILE_STATS_NORMS", "1") != "0"
         self._packed = None
         self._packed_sig = None
-        self._ws = _Workspace()
+        self._ws = Workspace()
         self._am = None              # the amax arena of the forward pass in flight (see PUNetG.forward_with_shifts)
         self._window_cache = {}
         self.exact_input_layer = False   # see PUNetG.exact_input_layer
@@ -673,11 +675,7 @@ class ADM(torch.nn.Module):
     @ops.device_guard
     def forward(self, x, t, y=None):
         """adm.py:199-216.  Top-level call: guarded (see PUNetG.forward)."""
-        out = self.forward_unguarded(x, t, y)
-        if precision.needs_escalation(self, out, x):
-            precision.escalate(self)
-            out = self.forward_unguarded(x, t, y)
-        return out
+        return runtime.guarded_forward(self, self.forward_unguarded, x, t, y)
 
     def check_field_size(self, shape):
         """H and W must divide by transition_scale_factor ** (number of transitions), else the decoder's resampled levels miss
@@ -729,8 +727,8 @@ class ADM(torch.nn.Module):
         for b in blocks:
             convs += [b.conv1, b.conv2, b.convresidual]
         attns = [b.attn for b in blocks if hasattr(b, "attn")]
-        sig = (self.conv_precision, getattr(self, "upsample_parity", True), self.exact_input_layer) + tuple((m.weight.data_ptr(), m.weight._version) for m in convs) + tuple(
-            (a.mhattn.in_proj_weight.data_ptr(), a.mhattn.in_proj_weight._version) for a in attns)
+        sig = weights_signature([m.weight for m in convs] + [a.mhattn.in_proj_weight for a in attns],
+                                self.conv_precision, getattr(self, "upsample_parity", True), self.exact_input_layer)
         if self._packed is not None and sig == self._packed_sig:
             return self._packed
         pk = {}
@@ -931,31 +929,11 @@ class ADM(torch.nn.Module):
 
     def _attention(self, att, x, pk, ws, tile_stats=None, in_amax=None, out_amax=None):
         """TwoDimensionalAttention.forward (attention.py:67-72,82-90), channel-major; amax rows as PUNetG._attention."""
-        B, E, Hh, Ww = x.shape
-        L = Hh * Ww
         m = att.mhattn
-        am = self._am
-        h3 = am is not None and pk[(id(att), "in")].kind == "fp16x3"
-        a_qkv, a_o = (am.rows(2), am.row()) if h3 else (None, None)
-        akw = (lambda **kw: kw) if h3 else (lambda **kw: {})
-        split = 2 * E if E % 32 == 0 else 0                           # one exponent for q and k, one for v
-        qkv = ops.conv(x, pk[(id(att), "in")], bias=m.in_proj_bias, out=ws.take((B, 3 * E, Hh, Ww), x.device),
-                       **akw(in_amax=self._raw_amax(x, in_amax) if h3 else None, out_amax=a_qkv if split else None, amax_split=split))
-        if h3 and not split:
-            ops.absmax_rows(qkv[:, :2 * E], out=a_qkv[:B])
-            ops.absmax_rows(qkv[:, 2 * E:], out=a_qkv[B:])
-        nws = ops.attention_workspace_floats(B, E, L, self.conv_precision, heads=m.num_heads)
-        aws = ws.take((nws,), x.device) if nws else None
-        o = ops.attention(qkv.view(B, 3 * E, L), E, out=ws.take((B, E, L), x.device),
-                          precision=self.conv_precision, workspace=aws, heads=m.num_heads, **akw(in_amax=a_qkv, out_amax=a_o))
-        if aws is not None:
-            ws.give(aws)
-        y = ops.conv(o.view(B, E, Hh, Ww), pk[(id(att), "out")], bias=m.out_proj.bias,
-                     res1=x if self.config.attn_residual else None, tile_stats=tile_stats,
-                     out=ws.take(x.shape, x.device), **akw(in_amax=a_o, out_amax=out_amax))
-        ws.give(qkv)
-        ws.give(o)
-        return y
+        return runtime.attention(x, pk[(id(att), "in")], m.in_proj_bias, pk[(id(att), "out")], m.out_proj.bias, E=x.shape[1],
+                                 heads=getattr(m, "num_heads", 1), precision=self.conv_precision, ws=ws, am=self._am,
+                                 in_amax=in_amax, out_amax=out_amax, res1=x if self.config.attn_residual else None,
+                                 tile_stats=tile_stats)
 
     def forward_with_shifts(self, x, shifts, row=None, out=None):
         """UNet body given the per-block FiLM rows (see PUNetG.forward_with_shifts)."""
@@ -968,14 +946,7 @@ class ADM(torch.nn.Module):
         it = iter(range(len(shifts)))
 
         def film():
-            s = shifts[next(it)]
-            if row is not None:
-                if s.dim() == 3:                       # [n_evals, B, 2C]: per-sample conditions in the planned sampler
-                    return s[row]
-                return s[row:row + 1]
-            if s.shape[0] not in (1, B):
-                raise ValueError("time embedding batch does not match x")
-            return s
+            return shift_rows(shifts[next(it)], row, B)
 
         dev = x.device
         H, W = x.shape[2:]
@@ -989,7 +960,7 @@ class ADM(torch.nn.Module):
         # activation exponents of the raw-input launches (input layer, every block's convresidual, the attention, a wide
         # output layer): rows of one arena per forward, filled by the producers' epilogues -- see PUNetG.forward_with_shifts
         h3 = self.conv_precision == "fp16x3"
-        am = self._am = _AmaxArena(ws, B, dev, zero=self.exact_input_layer) if h3 else None     # else zeroed by the input layer's reduction
+        am = self._am = AmaxArena(ws, B, dev, zero=self.exact_input_layer) if h3 else None     # else zeroed by the input layer's reduction
 
         def slot():
             return am.row() if h3 else None

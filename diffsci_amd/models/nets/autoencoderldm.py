@@ -25,6 +25,7 @@ import torch
 
 from ... import ops
 from ..._native import DS_LOAD_PLAIN, DS_LOAD_UPSAMPLE2
+from . import runtime
 
 NUM_GROUPS = 32
 EPS = 1e-6
@@ -66,8 +67,7 @@ class _Launcher(torch.nn.Module):
         return bool(self.fuse_norm) and self.conv_precision == "fp16x3" and self._dim == 2
 
     def _cached(self, name, tensors, make):
-        # inference tensors (a module built under torch.inference_mode) carry no version counter and cannot be written in place
-        sig = (self.conv_precision,) + tuple((t.data_ptr(), 0 if t.is_inference() else t._version, str(t.device)) for t in tensors)
+        sig = runtime.weights_signature(tensors, self.conv_precision)
         hit = self._packs.get(name)
         if hit is None or hit[0] != sig:
             with torch.no_grad():
@@ -102,14 +102,18 @@ class _Launcher(torch.nn.Module):
             return ops.conv3d_mfma(x, packs, bias=m.bias, load_mode=mode, res1=res1)
         return ops.conv3d(x, m.weight, bias=m.bias, load_mode=mode, res1=res1)       # thin layers / exact fp32
 
-    def _conv1(self, name, weights, biases, x, res1=None, tile_stats=None, **amax):
-        """1x1(x1) convolution of x [B, C, (D*)H, W] by the row-wise concatenation of `weights`."""
+    def _pack1(self, name, weights, biases):
+        """(packing, bias) of the 1x1(x1) convolution by the row-wise concatenation of `weights`."""
         prec = "fp16x3" if self.conv_precision == "fp16x3" else "fp32"
 
         def make():
             w = torch.cat([t.detach().reshape(t.shape[0], t.shape[1], 1, 1) for t in weights], dim=0).contiguous()
             return ops.pack_conv(w, prec), torch.cat([t.detach() for t in biases]).contiguous()
-        pk, bias = self._cached(name, tuple(weights) + tuple(biases), make)
+        return self._cached(name, tuple(weights) + tuple(biases), make)
+
+    def _conv1(self, name, weights, biases, x, res1=None, tile_stats=None, **amax):
+        """That convolution of x [B, C, (D*)H, W]."""
+        pk, bias = self._pack1(name, weights, biases)
         kw = amax if pk.kind == "fp16x3" else {}
         return ops.conv(x, pk, bias=bias, res1=res1, tile_stats=tile_stats, **kw)
 
@@ -208,18 +212,12 @@ class AttnBlock(_Launcher):
               else ops.groupnorm_stats(x, G, EPS))
         a_in = ops.amax_new(B, x.device) if h3 else None
         hn = ops.groupnorm_apply(x, st, self.norm.weight, self.norm.bias, G, act=False, out_amax=a_in)
-        # one exponent for q and k, one for v, left by the in-projection where its split falls on a channel tile (2C % 64 == 0: every C
-        # that 32 groups divide; with fewer groups C may be 24, 48, ...: the attention then reduces q, k, v itself where it needs them)
-        split = 2 * C if (2 * C) % 64 == 0 else 0
-        a_qkv, a_o = (ops.amax_new(2 * B, x.device) if split else None, ops.amax_new(B, x.device)) if h3 else (None, None)
-        qkv = self._conv1("qkv", (self.q.weight, self.k.weight, self.v.weight), (self.q.bias, self.k.bias, self.v.bias),
-                          self._v4(hn), in_amax=a_in, out_amax=a_qkv, amax_split=split)
-        akw = dict(in_amax=a_qkv, out_amax=a_o) if h3 else {}
-        o = ops.attention(qkv.view(B, 3 * C, L), C, precision=self.conv_precision, **akw)           # logits / sqrt(C)
+        w_in, b_in = self._pack1("qkv", (self.q.weight, self.k.weight, self.v.weight), (self.q.bias, self.k.bias, self.v.bias))
+        w_out, b_out = self._pack1("proj_out", (self.proj_out.weight,), (self.proj_out.bias,))
         x4 = self._v4(x)
         os_ = self._tiles(B, C, x.shape[2:], x.device)
-        out = self._conv1("proj_out", (self.proj_out.weight,), (self.proj_out.bias,), o.view(x4.shape), res1=x4, tile_stats=os_,
-                          in_amax=a_o)
+        out = runtime.attention(self._v4(hn), w_in, b_in, w_out, b_out, E=C, heads=1, precision=self.conv_precision,
+                                in_amax=a_in, res1=x4, tile_stats=os_)                            # one head: logits / sqrt(C)
         return out.view(x.shape), os_
 
     @ops.device_guard

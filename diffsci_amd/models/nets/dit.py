@@ -24,8 +24,9 @@ LayerNorm, the in-projection, the attention, the SiLU); the slots are rows of on
 import torch
 
 from ... import ops
-from . import precision
-from .punetg import _AmaxArena, _Fourier, _Workspace
+from . import runtime
+from .punetg import _Fourier
+from .runtime import AmaxArena, Workspace, weights_signature
 
 
 class _ResnetTimeBlock(torch.nn.Module):
@@ -76,14 +77,6 @@ class _DiTCore(torch.nn.Module):
         self.blocks = torch.nn.ModuleList([_DiTBlock(nembed, nheads, mlp_factor) for _ in range(nblocks)])
 
 
-class _Arena(_AmaxArena):
-    """The forward pass's amax slots, sized by the number of blocks (the arena's row count is part of its workspace key)."""
-
-    def __init__(self, ws, B, dev, rows):
-        self.ROWS = rows
-        super().__init__(ws, B, dev)
-
-
 # chunk6 of adaln_modulation's output (difftransformer.py:163-168)
 SHIFT_MSA, SCALE_MSA, GATE_MSA, SHIFT_MLP, SCALE_MLP, GATE_MLP = range(6)
 _ROWS_PER_BLOCK = 6      # amax rows a block takes: norm1, q k | v, attention, norm2, SiLU
@@ -113,7 +106,7 @@ class DiffusionTransformer(torch.nn.Module):
         self.auto_precision = True           # see PUNetG.auto_precision
         self._packed = None
         self._packed_sig = None
-        self._ws = _Workspace()
+        self._ws = Workspace()
         self._arena_rows = max(8, _ROWS_PER_BLOCK * len(self.core.blocks))
 
     # ------------------------------------------------------------------ reference surface
@@ -131,11 +124,7 @@ class DiffusionTransformer(torch.nn.Module):
     @ops.device_guard
     def forward(self, x, t):
         """difftransformer.py:226-236.  Top-level call: guarded (see PUNetG.forward)."""
-        out = self.forward_unguarded(x, t)
-        if precision.needs_escalation(self, out, x):
-            precision.escalate(self)
-            out = self.forward_unguarded(x, t)
-        return out
+        return runtime.guarded_forward(self, self.forward_unguarded, x, t)
 
     @ops.device_guard
     def forward_unguarded(self, x, t):
@@ -169,7 +158,7 @@ class DiffusionTransformer(torch.nn.Module):
         lin = []
         for b in self.core.blocks:
             lin += [b.attn.attn.in_proj_weight, b.attn.attn.out_proj.weight, b.mlp[0].weight, b.mlp[2].weight]
-        sig = (self.conv_precision,) + tuple((w.data_ptr(), w._version) for w in lin)
+        sig = weights_signature(lin, self.conv_precision)
         if self._packed is not None and sig == self._packed_sig:
             return self._packed
         if self.conv_precision not in ops.CONV_PRECISIONS:
@@ -188,42 +177,29 @@ class DiffusionTransformer(torch.nn.Module):
         dev = x.device
         mh = blk.attn.attn
         h3 = am is not None
-        akw = (lambda **kw: kw) if h3 else (lambda **kw: {})
 
-        def slot(n=1):
-            return (am.row() if n == 1 else am.rows(n)) if h3 else None
+        def amax_kw(**kw):                                              # in_amax / out_amax are arguments of the fp16x3 kernels only
+            return kw if h3 else {}
 
         def g4(t):
             return t.view(B, t.shape[1], Hp, Wp)
 
         # x += gate_msa * attn(modulate(norm1(x), shift_msa, scale_msa))
-        a_n = slot()
+        a_n = am.row() if h3 else None
         a = ops.token_layernorm(x, blk.norm1.weight, blk.norm1.bias, mod, SHIFT_MSA, SCALE_MSA, row, eps=blk.norm1.eps,
                                 out=ws.take((B, E, L), dev), out_amax=a_n)
-        a_qkv, a_o = slot(2), slot()
-        split = 2 * E if E % 32 == 0 else 0                           # one exponent for q and k, one for v
-        qkv = ops.conv(g4(a), pk[id(mh.in_proj_weight)], bias=mh.in_proj_bias, out=ws.take((B, 3 * E, Hp, Wp), dev),
-                       **akw(in_amax=a_n, out_amax=a_qkv if split else None, amax_split=split))
-        if h3 and not split:
-            ops.absmax_rows(qkv[:, :2 * E], out=a_qkv[:B])
-            ops.absmax_rows(qkv[:, 2 * E:], out=a_qkv[B:])
-        nws = ops.attention_workspace_floats(B, E, L, self.conv_precision, heads=mh.num_heads)
-        aws = ws.take((nws,), dev) if nws else None
-        o = ops.attention(qkv.view(B, 3 * E, L), E, out=a, precision=self.conv_precision, workspace=aws, heads=mh.num_heads,
-                          **akw(in_amax=a_qkv, out_amax=a_o))
-        if aws is not None:
-            ws.give(aws)
-        y = ops.conv(g4(o), pk[id(mh.out_proj.weight)], bias=mh.out_proj.bias, out=ws.take((B, E, Hp, Wp), dev), **akw(in_amax=a_o))
-        ws.give(qkv)
+        y = runtime.attention(g4(a), pk[id(mh.in_proj_weight)], mh.in_proj_bias, pk[id(mh.out_proj.weight)], mh.out_proj.bias,
+                              E=E, heads=mh.num_heads, precision=self.conv_precision, ws=ws, am=am, in_amax=a_n,
+                              attn_out=a)                             # the attention output overwrites the norm buffer
         ops.token_gate(x, y.view(B, E, L), mod, GATE_MSA, row, out=x)
         # x += gate_mlp * mlp(modulate(norm2(x), shift_mlp, scale_mlp))
-        a_n = slot()
+        a_n = am.row() if h3 else None
         ops.token_layernorm(x, blk.norm2.weight, blk.norm2.bias, mod, SHIFT_MLP, SCALE_MLP, row, eps=blk.norm2.eps, out=a, out_amax=a_n)
         h = ops.conv(g4(a), pk[id(blk.mlp[0].weight)], bias=blk.mlp[0].bias, out=ws.take((B, blk.nmlp, Hp, Wp), dev),
-                     **akw(in_amax=a_n))
-        a_h = slot()
+                     **amax_kw(in_amax=a_n))
+        a_h = am.row() if h3 else None
         ops.silu_amax(h, out=h, out_amax=a_h)
-        ops.conv(h, pk[id(blk.mlp[2].weight)], bias=blk.mlp[2].bias, out=y, **akw(in_amax=a_h))
+        ops.conv(h, pk[id(blk.mlp[2].weight)], bias=blk.mlp[2].bias, out=y, **amax_kw(in_amax=a_h))
         ws.give(h)
         ops.token_gate(x, y.view(B, E, L), mod, GATE_MLP, row, out=x)
         ws.give(a)
@@ -243,7 +219,7 @@ class DiffusionTransformer(torch.nn.Module):
         Hp, Wp = H // p, W // p
         dev = x.device
         h3 = self.conv_precision == "fp16x3"
-        am = _Arena(ws, B, dev, self._arena_rows) if h3 else None                  # one fill launch zeroes every slot of the pass
+        am = AmaxArena(ws, B, dev, rows=self._arena_rows) if h3 else None                  # one fill launch zeroes every slot of the pass
         try:
             tok = ops.patch_embed(x, self.embed.weight, self.embed.bias, p, out=ws.take((B, E, Hp * Wp), dev))
             for blk, s in zip(self.core.blocks, shifts):

@@ -22,6 +22,8 @@ import warnings
 
 import torch
 
+from . import runtime       # (runtime imports this module too: both sides use the other at call time only)
+
 RANGE_FREE = "bf16x6"
 
 
@@ -116,8 +118,7 @@ def norms_in_window(cache, key, norms):
     image / standalone routes this check serves pass in_amax = NORMALISED and lose accuracy gracefully there (absolute error
     2^-25 of unit scale, a tensor that carries no signal at fp32's own resolution of the surrounding unit-scale terms).  Stated in
     INTEGRATION.md.  Host check (one sync), cached per parameter version in `cache`."""
-    sig = tuple((t.data_ptr(), t._version) for n in norms for t in (getattr(n, "weight", None), getattr(n, "bias", None))
-                if t is not None)
+    sig = runtime.weights_signature(t for n in norms for t in (getattr(n, "weight", None), getattr(n, "bias", None)) if t is not None)
     hit = cache.get(key)
     if hit is not None and hit[0] == sig:
         return hit[1]

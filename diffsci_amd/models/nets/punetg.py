@@ -24,8 +24,9 @@ import torch
 
 from ... import ops
 from ..._native import DS_LOAD_MAXPOOL2, DS_LOAD_UPSAMPLE2
-from . import precision
+from . import precision, runtime
 from .punetg_config import PUNetGConfig, scale_factor
+from .runtime import AmaxArena, Workspace, require_eval, shift_rows, weights_signature
 
 
 class _AffineHolder(torch.nn.Module):
@@ -204,97 +205,6 @@ class _ConditionDrop(torch.nn.Module):
             self.register_buffer("null_embedding", torch.zeros(1, hidden_dim))
 
 
-def require_eval(net, *rates):
-    """Dropout, condition dropout and ConditionDrop are the identity in eval mode -- the only mode the sampling path
-    implements.  A network left in training mode with a non-zero rate would silently differ from the reference."""
-    if net.training and any(r for r in rates if r):
-        raise NotImplementedError("dropout / cond_dropout / cond_drop > 0 in training mode are outside the HIP sampling "
-                                  "path: call .eval() (the reference samples under eval() too)")
-
-
-class _Workspace:
-    """Shape-keyed pool of device buffers.  A forward pass takes and gives buffers in a fixed
-    order, so after the first pass no allocation happens -- a requirement for hipGraph capture."""
-
-    def __init__(self):
-        self.free = {}
-        self.frozen = False
-        self.bytes = 0
-
-    def take(self, shape, device):
-        key = (tuple(shape), str(device))
-        lst = self.free.get(key)
-        if lst:
-            return lst.pop()
-        if self.frozen:
-            raise RuntimeError(f"workspace is frozen (graph captured) but a new buffer {shape} was requested")
-        with torch.inference_mode(False):    # a normal tensor even when the sampler runs under inference_mode: the pool
-            t = torch.empty(shape, dtype=torch.float32, device=device)   # outlives the call and serves eager forwards too
-        self.bytes += t.numel() * 4
-        return t
-
-    def give(self, t):
-        self.free.setdefault((tuple(t.shape), str(t.device)), []).append(t)
-
-
-class _AmaxArena:
-    """Per-forward rows of "amax" slots (ops.py: per-sample max |x| as float bits, the activation exponents of the fp16x3
-    kernels' raw-input launches), taken from the workspace and zeroed by ONE fill launch; producers' epilogues merge into a
-    row (out_amax), the raw-input consumer reads it (in_amax)."""
-    ROWS = 256
-
-    def __init__(self, ws, B, dev, zero=True):
-        self.ws, self.buf = ws, ws.take((self.ROWS, max(B, 1)), dev)
-        self.i32 = self.buf.view(torch.int32)
-        if zero:                                  # zero=False: the caller's first act is of_input(), which zeroes the arena itself
-            ops.amax_zero(self.i32)
-        self.zeroed = zero
-        self.n = 0
-
-    def row(self):
-        if not self.zeroed:
-            ops.amax_zero(self.i32)
-            self.zeroed = True
-        if self.n >= self.ROWS:
-            raise RuntimeError("amax arena exhausted")
-        self.n += 1
-        return self.i32[self.n - 1]
-
-    def rows(self, n):
-        """n consecutive rows as one [n * B] tensor."""
-        if not self.zeroed:
-            ops.amax_zero(self.i32)
-            self.zeroed = True
-        if self.n + n > self.ROWS:
-            raise RuntimeError("amax arena exhausted")
-        self.n += n
-        return self.i32[self.n - n:self.n].view(-1)
-
-    def of(self, x, rows=None):
-        """Slots filled by a reduction over x (a tensor no epilogue of ours produced)."""
-        return ops.absmax_rows(x, rows, out=self.row())
-
-    def of_input(self, x, flag, wmax):
-        """The same for a network input x [B, C, ...] (c_in * x next to raw user fields): per-channel maxima first, `flag` raised
-        when one exponent per sample cannot serve the input layer given its weights (ops.absmax_channels; precision.input_layer_flag)."""
-        C = x.shape[1]
-        if not self.zeroed:
-            if self.n == 0 and C <= 64 and x[0].numel() <= ops.INPUT_AMAX_MAX_FLOATS and x.shape[0] == self.i32.shape[1]:
-                self.n, self.zeroed = 1, True
-                return ops.input_amax(self.i32, 0, x, flag, wmax)      # one launch: zero the arena, reduce, apply the channel criterion
-            ops.amax_zero(self.i32)
-            self.zeroed = True
-        if self.n + C + 1 > self.ROWS:
-            return self.of(x)
-        out = self.row()
-        scratch = self.i32[self.n:self.n + C].view(-1)
-        self.n += C
-        return ops.absmax_channels(x, out, scratch, flag, wmax)
-
-    def release(self):
-        self.ws.give(self.buf)
-
-
 class _FieldShifts:
     """Per-pixel time shifts, computed where they are used.  A field-valued conditional embedding makes the time embedding a
     field te [B, C, He, We] (punetg.py:405-410) and every block's ResnetTimeBlock a per-pixel MLP (commonlayers.py:537-546)
@@ -309,7 +219,7 @@ class _FieldShifts:
         (ops.cornerpool_f), so their sum at the field's own resolution is never written."""
         self.te, self.ws, self.te_owned = te, ws, owned
         self.rows, self.batch = rows, te.shape[0] if batch is None else batch
-        self.am = _AmaxArena(ws, self.batch, te.device) if h3 else None
+        self.am = AmaxArena(ws, self.batch, te.device) if h3 else None
         self.levels = {}
 
     def _level_nd(self, dims):
@@ -429,7 +339,7 @@ class PUNetG(torch.nn.Module):
         self.norm_images = os.environ.get("DIFFSCI_NORM_IMAGES", "1") != "0"
         self._packed = None
         self._packed_sig = None
-        self._ws = _Workspace()
+        self._ws = Workspace()
         self._am = None              # the amax arena of the forward pass in flight
         self._window_cache = {}
         # set by precision.escalate_input when the input's channels differ by more than 2^14 in magnitude within a sample
@@ -581,11 +491,7 @@ class PUNetG(torch.nn.Module):
         """punetg.py:389-416.  x [B, Cin, H, W]; t [B] noise conditioning; y optional condition.  A top-level call: the result
         is checked by the domain guards (nets/precision.py: one device reduction and a host read) and recomputed if one fires;
         the sampler's eager path calls forward_unguarded and checks once per run."""
-        out = self.forward_unguarded(x, t, y)
-        if precision.needs_escalation(self, out, x):
-            precision.escalate(self)
-            out = self.forward_unguarded(x, t, y)
-        return out
+        return runtime.guarded_forward(self, self.forward_unguarded, x, t, y)
 
     def check_field_size(self, shape):
         """With transition_scale_factor f != 2 every spatial side must divide by f ** (number of transitions), else a decoder
@@ -689,7 +595,7 @@ class PUNetG(torch.nn.Module):
 
     def _timeblock_convs(self):
         lins = list(self._timeblock_linears())
-        sig = (self.conv_precision,) + tuple((l.weight.data_ptr(), l.weight._version) for l in lins)
+        sig = weights_signature([l.weight for l in lins], self.conv_precision)
         if getattr(self, "_tb_packed_sig", None) != sig:
             with torch.no_grad():
                 self._tb_packed = {}
@@ -708,18 +614,8 @@ class PUNetG(torch.nn.Module):
 
     def time_shifts(self, te):
         """Per-block ResnetTimeBlock(te): list of [M, C_block] tensors in block order."""
-        out = []
-        pk = self.packed_weights() if self.mp else None
-
-        def wgt(lin):
-            return pk[(id(lin), "eff")] if pk is not None else lin.weight
-
-        for blk in self._resblocks():
-            n = blk.timeblock.net
-            h = ops.linear(te, wgt(n[0]), n[0].bias, act=1)
-            h = ops.linear(h, wgt(n[2]), n[2].bias, act=1)
-            out.append(ops.linear(h, wgt(n[4]), n[4].bias, act=0))
-        return out
+        pk = self.packed_weights() if self.mp else None                # once per call, not once per block
+        return [self._shift_of(blk, te, pk) for blk in self._resblocks()]
 
     def _resblocks(self):
         for lv in self.downward_blocks:
@@ -735,8 +631,10 @@ class PUNetG(torch.nn.Module):
     # stages themselves (e.g. the encoder / decoder halves of punetg_encdec.py).  Eager launches of the same
     # kernels as forward(); te is the [B, model_channels] embedding (time projection + condition); results are
     # fresh tensors, never workspace buffers.
-    def _shift_of(self, blk, te):
-        pk = self.packed_weights() if self.mp else None
+    def _shift_of(self, blk, te, pk=None):
+        """ResnetTimeBlock(te) of one block -> [M, C_block]; pk: the packed weights, when the caller has them at hand."""
+        if pk is None and self.mp:
+            pk = self.packed_weights()
         n = blk.timeblock.net
         wgt = (lambda lin: pk[(id(lin), "eff")]) if pk is not None else (lambda lin: lin.weight)
         h = ops.linear(te, wgt(n[0]), n[0].bias, act=1)
@@ -842,7 +740,7 @@ class PUNetG(torch.nn.Module):
                         if self.inhouse_attn else [a.mhattn.in_proj_weight, a.mhattn.out_proj.weight])
         if self.mp:
             tracked += [lin.weight for lin in self._timeblock_linears()]
-        sig = (self.conv_precision, getattr(self, "upsample_parity", True), self.exact_input_layer) + tuple((t.data_ptr(), t._version) for t in tracked)
+        sig = weights_signature(tracked, self.conv_precision, getattr(self, "upsample_parity", True), self.exact_input_layer)
         if self._packed is not None and sig == self._packed_sig:
             return self._packed
         pk = {}
@@ -1082,18 +980,7 @@ class PUNetG(torch.nn.Module):
         def sh():
             if lazy_shifts is not None:                # per-pixel shifts: each block evaluates its own (_field_shift)
                 return lazy_shifts
-            s = shifts[next(it)]
-            if s.dim() == 4:                           # [B, C, He, We]: a field of shifts handed over as a tensor (allocates: not for captured runs)
-                return s
-            if row is not None:
-                if s.dim() == 3:                       # [n_evals, B, C]: per-sample conditions in the planned sampler
-                    if s.shape[1] != B:
-                        raise ValueError("time embedding batch does not match x")
-                    return s[row]
-                return s[row:row + 1]
-            if s.shape[0] not in (1, B):
-                raise ValueError("time embedding batch does not match x")
-            return s
+            return shift_rows(shifts[next(it)], row, B)    # a field handed over as a tensor allocates: not for captured runs
 
         def give(t, ts):
             ws.give(t)
@@ -1107,7 +994,7 @@ class PUNetG(torch.nn.Module):
         h3 = self.conv_precision == "fp16x3"
         # (the arena is zeroed by the input layer's own reduction launch when that is the first thing the forward does)
         lazy = h3 and not isinstance(self.convin, _FourierInput) and not self.exact_input_layer
-        am = self._am = _AmaxArena(ws, B, dev, zero=not lazy) if h3 else None
+        am = self._am = AmaxArena(ws, B, dev, zero=not lazy) if h3 else None
 
         def slot(needed=True):
             return am.row() if (h3 and needed) else None
@@ -1278,16 +1165,7 @@ class PUNetG(torch.nn.Module):
         k1, k2 = self.norm_kinds
 
         def sh():
-            s = shifts[next(it)]
-            if row is not None:
-                if s.dim() == 3:                       # [n_evals, B, C]: per-sample conditions in the planned sampler
-                    if s.shape[1] != B:
-                        raise ValueError("time embedding batch does not match x")
-                    return s[row]
-                return s[row:row + 1]
-            if s.shape[0] not in (1, B):
-                raise ValueError("time embedding batch does not match x")
-            return s
+            return shift_rows(shifts[next(it)], row, B)
 
         # Norm folding on volumes (round 2; fp16x3, 3x3x3 kernels; round 3: periodic padding too): every activation travels with the partial
         # sums its producer's slice -> volume copy left (hs); a block whose input has them runs ops.resblock3d_fused --
@@ -1451,43 +1329,17 @@ class PUNetG(torch.nn.Module):
         """TwoDimensionalAttention.forward (attention.py:67-72,82-90), channel-major throughout.  The block's three launches
         read raw tensors: x (in_amax: its producer's row, or None = reduced here), qkv and the attention output, whose
         exponents travel from epilogue to loader through rows of the forward's arena."""
-        B, E, Hh, Ww = x.shape
-        L = Hh * Ww
         m = att.mhattn
         in_bias = None if self.inhouse_attn else m.in_proj_bias    # the in-house attention has no biases
         out_bias = None if self.inhouse_attn else m.out_proj.bias
         am = self._am if self.conv_precision == "fp16x3" else None
         own = None
         if am is None and self.conv_precision == "fp16x3":           # called outside forward_with_shifts (the 3-D path sets its own)
-            own = am = _AmaxArena(ws, B, x.device)
-        split = 2 * E if E % 32 == 0 else 0                           # one exponent for q and k, one for v (E % 32: the fp16x3 attention)
-        a_qkv = am.rows(2) if am is not None else None
-        a_o = am.row() if am is not None else None
-        if am is not None and in_amax is None:
-            in_amax = am.of(x)
-        direct = not self.cosine_attn and split > 0
-        qkv = ops.conv(x, pk[(id(att), "in")], bias=in_bias, out=ws.take((B, 3 * E, Hh, Ww), x.device),
-                       **self._amax_kw(in_amax=in_amax, out_amax=a_qkv if direct else None, amax_split=split if direct else 0))
-        if self.cosine_attn:
-            # cosine_similarity (attention.py:362-372): unit queries and keys, logits without 1/sqrt(E) -- the
-            # attention kernels scale by 1/sqrt(E), which the queries' gain cancels
-            ops.token_l2_normalize(qkv.view(B, 3 * E, L), 0, E, eps=1e-8, gain=math.sqrt(E))
-            ops.token_l2_normalize(qkv.view(B, 3 * E, L), E, E, eps=1e-8, gain=1.0)
-        if am is not None and not direct:                             # q and k were rewritten, or a head width the epilogue cannot split: measure
-            ops.absmax_rows(qkv[:, :2 * E], out=a_qkv[:B])
-            ops.absmax_rows(qkv[:, 2 * E:], out=a_qkv[B:])
-        nws = ops.attention_workspace_floats(B, E, L, self.conv_precision)
-        aws = ws.take((nws,), x.device) if nws else None
-        o = ops.attention(qkv.view(B, 3 * E, L), E, out=ws.take((B, E, L), x.device),
-                          precision=self.conv_precision, workspace=aws, **self._amax_kw(in_amax=a_qkv, out_amax=a_o))
-        if aws is not None:
-            ws.give(aws)
-        res1 = x if self.config.attn_residual else None
-        y = ops.conv(o.view(B, E, Hh, Ww), pk[(id(att), "out")], bias=out_bias,
-                     res1=res1, res2=res2, tile_stats=tile_stats, out=ws.take(x.shape, x.device),
-                     **self._amax_kw(in_amax=a_o, out_amax=out_amax))
-        ws.give(qkv)
-        ws.give(o)
+            own = am = AmaxArena(ws, x.shape[0], x.device)
+        y = runtime.attention(x, pk[(id(att), "in")], in_bias, pk[(id(att), "out")], out_bias, E=x.shape[1],
+                              heads=getattr(m, "num_heads", 1), precision=self.conv_precision, ws=ws, am=am, in_amax=in_amax,
+                              out_amax=out_amax, res1=x if self.config.attn_residual else None, res2=res2, tile_stats=tile_stats,
+                              cosine=self.cosine_attn)
         if own is not None:
             own.release()
         return y

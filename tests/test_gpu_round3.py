@@ -510,7 +510,7 @@ def test_input_maxima_one_launch_and_fallback_agree(dev, ops, shape):
     """ds_input_amax (one launch: zero the arena, reduce, channel criterion) against the three-launch route it replaces
     (fill + ds_absmax_channels) and against torch: same rows, same flag -- on aligned, odd-sized and beyond-the-limit inputs
     (the last shape exceeds INPUT_AMAX_MAX_FLOATS per sample, which the arena routes to the fallback)."""
-    from diffsci_amd.models.nets.punetg import _AmaxArena, _Workspace
+    from diffsci_amd.models.nets.runtime import AmaxArena as _AmaxArena, Workspace as _Workspace
     g = torch.Generator().manual_seed(sum(shape))
     B, C = shape[:2]
     x = torch.randn(*shape, generator=g).to(dev)

@@ -8,21 +8,31 @@ from . import _native as N
 from ._native import EvalCoef  # noqa: F401  (re-export)
 
 
+def _off_device(t):
+    """Why tensor t cannot be handed to a launch on the current stream: "host" when it is not in GPU memory, "other" when it
+    lives on another GPU than the current one; None for a device tensor on the current device.  The one place that decides."""
+    if not t.is_cuda:
+        return "host"
+    return None if t.device.index == torch.cuda.current_device() else "other"
+
+
 def require_device(t, what="tensor"):
     if not isinstance(t, torch.Tensor):
         raise TypeError(f"{what} must be a torch.Tensor")
-    if not t.is_cuda:
+    off = _off_device(t)
+    if not off and t.dtype == torch.float32:
+        return
+    if off == "host":
         raise RuntimeError(
             f"{what} lives on {t.device}: diffsci_amd computes only on an AMD GPU through "
             "libdiffsci_hip.so (there is no CPU path; move the module and inputs to 'cuda').")
     if t.dtype != torch.float32:
         raise TypeError(f"{what} has dtype {t.dtype}; the HIP path is fp32 only")
-    if t.device.index != torch.cuda.current_device():
-        # the C ABI launches on the stream it is handed and never switches devices: a launch on cuda:0's stream
-        # with cuda:1 pointers would fault (or silently compute on the wrong GPU's copy of a kernel attribute)
-        raise RuntimeError(f"{what} lives on {t.device} but the current device is cuda:{torch.cuda.current_device()}: "
-                           "wrap the call in `with torch.cuda.device(tensor.device):` (KarrasModule / SIModule / the "
-                           "networks do this for their own entry points)")
+    # the C ABI launches on the stream it is handed and never switches devices: a launch on cuda:0's stream
+    # with cuda:1 pointers would fault (or silently compute on the wrong GPU's copy of a kernel attribute)
+    raise RuntimeError(f"{what} lives on {t.device} but the current device is cuda:{torch.cuda.current_device()}: "
+                       "wrap the call in `with torch.cuda.device(tensor.device):` (KarrasModule / SIModule / the "
+                       "networks do this for their own entry points)")
 
 
 def on_device_of(t):
@@ -51,7 +61,8 @@ def device_guard(fn):
 def _p(t, what="tensor"):
     if t is None:
         return None
-    require_device(t, what)
+    if not isinstance(t, torch.Tensor) or _off_device(t) or t.dtype != torch.float32:
+        require_device(t, what)                  # raises, and says which (here only the test: one frame less per pointer)
     if not t.is_contiguous():
         raise ValueError(f"{what} must be contiguous")
     return t.data_ptr()
@@ -59,6 +70,163 @@ def _p(t, what="tensor"):
 
 def _stream():
     return torch.cuda.current_stream().cuda_stream
+
+
+# ---------------------------------------------------------------- the checking vocabulary of the wrappers below
+# The C side refuses NULL and non-positive sizes but cannot know how large a buffer is, so no pointer reaches the ABI without
+# an extent check made here.  Each decision is written once; a message that takes formatting is built only
+# when its check fails -- the eager paths pay Python per launch.
+def _out(out, shape, like, msg="out has shape {}, expected {}"):
+    """The output of a kernel that indexes by `shape`: a fresh fp32 tensor on like's device, or the given one verified.
+    msg is formatted with (the given shape, the expected one)."""
+    if out is None:
+        return torch.empty(shape, dtype=torch.float32, device=like.device)
+    if tuple(out.shape) != tuple(shape):
+        raise ValueError(msg.format(tuple(out.shape), tuple(shape)))
+    return out
+
+
+_STATS_MSG, _TABLE_MSG = "stats must be {1}", "table must be {1}"       # _out messages of the norm statistics and tables
+
+
+def _same_numel(*ts):
+    n = None
+    for t in ts:
+        if t is None:
+            continue
+        if n is None:
+            n = t.numel()
+        elif t.numel() != n:
+            raise ValueError(f"size mismatch: {t.numel()} vs {n} elements")
+    return n
+
+
+def _out_flat(out, *same, like=None):
+    """The flat twin, for kernels that index one range of n elements whatever the shapes (callers pass views of the same
+    size): a fresh tensor like `like` (default: the first of `same`), or the given one; all of `same` and out must hold the
+    same number of elements.  -> (out, n)."""
+    if out is None:
+        out = torch.empty_like(same[0] if like is None else like)
+    return out, _same_numel(*same, out)
+
+
+def _row_stride(t, B, width, msg):
+    """Per-sample rows [1 or B, width] (None: none) -> the stride in floats between the samples' rows: 0 when one row serves
+    all, else width.  msg is formatted with the shape given."""
+    if t is None:
+        return 0
+    if t.dim() != 2 or t.shape[1] != width or t.shape[0] not in (1, B):
+        raise ValueError(msg.format(tuple(t.shape)))
+    return 0 if t.shape[0] == 1 else width
+
+
+_SHIFT_MSG = "shift must be [1 or B, Cout]; got {}"      # every convolution's per-sample shift [1 or B, Cout]
+
+
+def _film_args(film, B, C):
+    """(scale pointer, shift pointer, stride) of FiLM rows [1 or B, 2C] (embed_linear(te)), or (None, None, 0)."""
+    if film is None:
+        return None, None, 0
+    stride = _row_stride(film, B, 2 * C, "film must be [1 or B, 2C]")
+    p = _p(film, "film")                 # on the device and contiguous: a strided view of a wider table has other rows
+    return p, p + 4 * C, stride
+
+
+def _residuals(shape, *rs):
+    for r in rs:
+        if r is not None and tuple(r.shape) != shape:
+            raise ValueError("residual shape mismatch")
+
+
+def _entries(t, n, msg, *fmt):
+    """A per-channel vector (bias, norm weight, ...) holds n entries; None passes.  msg.format(*fmt) on failure."""
+    if t is not None and t.numel() != n:
+        raise ValueError(msg.format(*fmt))
+
+
+def _affine(w, b, C, what):
+    """_entries for a norm's weight and bias (one frame for the pair: norms sit on the eager paths)."""
+    if w is not None and w.numel() != C:
+        raise ValueError(f"{what}: norm weight must have C={C} entries")
+    if b is not None and b.numel() != C:
+        raise ValueError(f"{what}: norm bias must have C={C} entries")
+
+
+def _gnorm1_inputs(stats, w, b, B, C, what):
+    """What a gnorm1 apply kernel reads next to x: stats [B, 2] (None for kind 2, the identity) and C-entry affines."""
+    if stats is not None and tuple(stats.shape) != (B, 2):
+        raise ValueError(f"{what}: stats must be {(B, 2)}; got {tuple(stats.shape)}")
+    _affine(w, b, C, what)
+
+
+def _tile_stats(ts, B, Cout, H, W, got=False):
+    """tile_stats of an fp16x3 convolution's [B, Cout, H, W] output (None passes)."""
+    if ts is not None and tuple(ts.shape) != (B, Cout, conv_tile_count(H, W), 4):
+        raise ValueError(f"tile_stats must be {(B, Cout, conv_tile_count(H, W), 4)}" + (f"; got {tuple(ts.shape)}" if got else ""))
+
+
+def _images(buf, B, C, H, W, msg, like=None):
+    """The pre-split image buffer of a [B, C, H, W] activation: conv_images_floats elements; like: allocate when None."""
+    n = conv_images_floats(B, C, H, W)
+    if buf is None and like is not None:
+        return torch.empty(n, dtype=torch.float32, device=like.device)
+    if buf.numel() != n:
+        raise ValueError(msg)
+    return buf
+
+
+def _groups(C, G, what):
+    G = int(G)
+    if G < 1 or C % G:
+        raise ValueError(f"{what}: C={C} is not a multiple of num_groups={G}")
+    return G
+
+
+def _workspace(workspace, nbytes, like, msg):
+    """Scratch of at least nbytes for a kernel: the given fp32 tensor verified, or a fresh one."""
+    if workspace is None:
+        return torch.empty(nbytes // 4, dtype=torch.float32, device=like.device)
+    if workspace.numel() * 4 < nbytes:
+        raise ValueError(msg)
+    return workspace
+
+
+def _load_sides(load_mode, sides):
+    """Output sides of a convolution whose loader pools or upsamples by two (AVGPOOL2 exists on fields only: the volume
+    kernels read it as a plain load)."""
+    if load_mode == N.DS_LOAD_PLAIN:
+        return sides
+    if load_mode == N.DS_LOAD_MAXPOOL2 or (load_mode == N.DS_LOAD_AVGPOOL2 and len(sides) == 2):
+        if any(s % 2 for s in sides):
+            raise ValueError("pooling load needs even input H, W" if len(sides) == 2 else "pooling load needs an even input volume")
+        return tuple(s // 2 for s in sides)
+    if load_mode == N.DS_LOAD_UPSAMPLE2:
+        return tuple(2 * s for s in sides)
+    return sides
+
+
+class _Scratch:
+    """The temporaries of one composed call: from the pool `ws` (take(shape, device) / give(tensor); a captured loop must not
+    allocate) or, ws=None, from torch's allocator.  give() hands back everything taken, in the order it was taken."""
+    __slots__ = ("ws", "device", "taken")
+
+    def __init__(self, ws, device):
+        self.ws, self.device, self.taken = ws, device, []
+
+    def take(self, shape):
+        if self.ws is None:
+            return torch.empty(shape, dtype=torch.float32, device=self.device)
+        t = self.ws.take(shape, self.device)
+        self.taken.append(t)
+        return t
+
+    def amax(self, rows):
+        """Zeroed amax slots (see below): a pool buffer cleared by a launch, or a fresh zeroed tensor."""
+        return amax_new(rows, self.device) if self.ws is None else amax_zero(self.take((rows,)).view(torch.int32))
+
+    def give(self):
+        for t in self.taken:
+            self.ws.give(t)
 
 
 # ---------------------------------------------------------------- per-sample activation exponents of the fp16x3 kernels
@@ -79,9 +247,10 @@ NORMALISED = _Normalised()
 def _pi(t, n, what="amax"):
     if t is None:
         return None
-    if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.int32 and t.is_contiguous() and t.numel() == n):
+    off = _off_device(t) if isinstance(t, torch.Tensor) else "host"
+    if off == "host" or not (t.dtype == torch.int32 and t.is_contiguous() and t.numel() == n):
         raise TypeError(f"{what} must be a contiguous int32 device tensor of {n} entries (float bits of per-sample max |x|)")
-    if t.device.index != torch.cuda.current_device():
+    if off:
         raise RuntimeError(f"{what} lives on another device than the current one")
     return t.data_ptr()
 
@@ -173,28 +342,14 @@ def _xin_numel(x, xin_out, copies):
         raise ValueError(f"xin_out holds {xin_out.numel()} elements; expected {x.numel() * (2 if copies == 2 else 1)}")
 
 
-def _same_numel(*ts):
-    n = None
-    for t in ts:
-        if t is None:
-            continue
-        if n is None:
-            n = t.numel()
-        elif t.numel() != n:
-            raise ValueError(f"size mismatch: {t.numel()} vs {n} elements")
-    return n
-
-
 def scale(x, s, out=None):
-    out = torch.empty_like(x) if out is None else out
-    n = _same_numel(x, out)
+    out, n = _out_flat(out, x)
     N.check(N.lib().ds_karras_scale(_p(out, "out"), _p(x, "x"), float(s), n, _stream()), "ds_karras_scale")
     return out
 
 
 def add(a, b, out=None):
-    out = torch.empty_like(a) if out is None else out
-    n = _same_numel(a, b, out)
+    out, n = _out_flat(out, a, b)
     N.check(N.lib().ds_add(_p(out), _p(a), _p(b), n, _stream()), "ds_add")
     return out
 
@@ -205,31 +360,29 @@ def mask_blend(x, y, mask, out=None):
     nps = x.numel() // max(B, 1)
     if y.shape != x.shape or mask.numel() != nps:
         raise ValueError(f"mask_blend: x {tuple(x.shape)}, y {tuple(y.shape)}, mask {tuple(mask.shape)}")
-    out = torch.empty_like(x) if out is None else out
+    out, _ = _out_flat(out, x)
     N.check(N.lib().ds_mask_blend(_p(out), _p(x), _p(y), _p(mask), nps, B, _stream()), "ds_mask_blend")
     return out
 
 
 def axpby(x, a, y=None, b=0.0, out=None):
     """a*x + b*y (y optional)."""
-    out = torch.empty_like(x) if out is None else out
-    _same_numel(x, y, out)
-    N.check(N.lib().ds_axpby(_p(out), _p(x), float(a), _p(y), float(b), x.numel(), _stream()), "ds_axpby")
+    out, n = _out_flat(out, x, y)
+    N.check(N.lib().ds_axpby(_p(out), _p(x), float(a), _p(y), float(b), n, _stream()), "ds_axpby")
     return out
 
 
 def div_scalar(x, s, out=None):
     """x / s."""
-    out = torch.empty_like(x) if out is None else out
-    N.check(N.lib().ds_div_scalar(_p(out), _p(x), float(s), x.numel(), _stream()), "ds_div_scalar")
+    out, n = _out_flat(out, x)
+    N.check(N.lib().ds_div_scalar(_p(out), _p(x), float(s), n, _stream()), "ds_div_scalar")
     return out
 
 
 def batchnorm_eval(x, mean, var, weight=None, bias=None, eps=1e-5, sigma=1.0, inverse=False, out=None):
     """DimensionAgnosticBatchNorm.forward / .unnorm with running statistics; x [B, C, *spatial]."""
     require_device(x, "x")
-    out = torch.empty_like(x) if out is None else out
-    _same_numel(x, out)
+    out, _ = _out_flat(out, x)
     B, C = x.shape[0], x.shape[1]
     HW = x.numel() // max(B * C, 1)
     nc = mean.numel()
@@ -242,22 +395,21 @@ def batchnorm_eval(x, mean, var, weight=None, bias=None, eps=1e-5, sigma=1.0, in
 
 def lerp_stack(x1, x2, n):
     """stack([x1 + (x2 - x1)*i/(n-1) for i in range(n)])."""
+    _same_numel(x1, x2)
     out = torch.empty((n,) + tuple(x1.shape), dtype=torch.float32, device=x1.device)
     N.check(N.lib().ds_lerp_stack(_p(out), _p(x1), _p(x2), int(n), x1.numel(), _stream()), "ds_lerp_stack")
     return out
 
 
 def drift(x, f, k, fu=None, out=None):
-    out = torch.empty_like(f) if out is None else out
-    n = _same_numel(x, f, fu, out)
+    out, n = _out_flat(out, x, f, fu, like=f)
     N.check(N.lib().ds_karras_drift(_p(out), _p(x), _p(f), _p(fu), ctypes.byref(k), n, _stream()),
             "ds_karras_drift")
     return out
 
 
 def score(x, f, k, fu=None, out=None):
-    out = torch.empty_like(f) if out is None else out
-    n = _same_numel(x, f, fu, out)
+    out, n = _out_flat(out, x, f, fu, like=f)
     N.check(N.lib().ds_karras_score(_p(out), _p(x), _p(f), _p(fu), ctypes.byref(k), n, _stream()),
             "ds_karras_score")
     return out
@@ -268,10 +420,10 @@ def _philox(philox):
     if philox is None:
         return None, 0
     state, offset = philox
-    if not (isinstance(state, torch.Tensor) and state.is_cuda and state.dtype == torch.int64 and state.numel() == 2
-            and state.is_contiguous()):
+    off = _off_device(state) if isinstance(state, torch.Tensor) else "host"
+    if off == "host" or not (state.dtype == torch.int64 and state.numel() == 2 and state.is_contiguous()):
         raise TypeError("philox state must be a contiguous int64[2] device tensor (seed, base offset)")
-    if state.device.index != torch.cuda.current_device():
+    if off:
         raise RuntimeError("philox state lives on another device than the current one")
     return state.data_ptr(), int(offset)
 
@@ -323,11 +475,10 @@ def churn(x, eps, coef, xhat_out, xin_out=None, c_in=1.0, philox=None, ratio=1.0
 
 
 def denoiser(x, f, c_out, c_skip, fu=None, guidance=1.0, out=None):
-    out = torch.empty_like(x) if out is None else out
     B = x.shape[0]
     if c_out.numel() != B or c_skip.numel() != B:
         raise ValueError("c_out / c_skip must have one entry per sample")
-    _same_numel(x, f, fu, out)
+    out, _ = _out_flat(out, x, f, fu)
     N.check(N.lib().ds_karras_denoiser(_p(out), _p(x), _p(f), _p(fu), float(guidance), float(1 - guidance),
                                        _p(c_out), _p(c_skip), B, x.numel() // max(B, 1), _stream()),
             "ds_karras_denoiser")
@@ -336,12 +487,11 @@ def denoiser(x, f, c_out, c_skip, fu=None, guidance=1.0, out=None):
 
 def inorm_silu(x, w, b, kind, eps=1e-5, out=None):
     """kind 0: GroupNorm(C, C)+SiLU, kind 1: GroupRMSNorm(C, C)+SiLU; x [B, C, *spatial]."""
-    out = torch.empty_like(x) if out is None else out
     B, C = x.shape[0], x.shape[1]
     HW = x.numel() // max(B * C, 1)
     if w is not None and (w.numel() != C or b.numel() != C):
         raise ValueError("norm affine parameters must have C entries")
-    _same_numel(x, out)
+    out, _ = _out_flat(out, x)
     N.check(N.lib().ds_inorm_silu(_p(out), _p(x), _p(w), _p(b), B, C, HW, float(eps), int(kind), _stream()),
             "ds_inorm_silu")
     return out
@@ -355,28 +505,11 @@ def conv3d(x, w, bias=None, shift=None, res1=None, res2=None, load_mode=N.DS_LOA
     Cout = w.shape[0]
     if tuple(w.shape) != (Cout, Cin, 3, 3, 3):
         raise ValueError(f"conv3d: weight must be [Cout, {Cin}, 3, 3, 3]; got {tuple(w.shape)}")
-    if load_mode == N.DS_LOAD_MAXPOOL2:
-        if Di % 2 or Hi % 2 or Wi % 2:
-            raise ValueError("pooling load needs an even input volume")
-        D, H, W = Di // 2, Hi // 2, Wi // 2
-    elif load_mode == N.DS_LOAD_UPSAMPLE2:
-        D, H, W = 2 * Di, 2 * Hi, 2 * Wi
-    else:
-        D, H, W = Di, Hi, Wi
-    if out is None:
-        out = torch.empty((B, Cout, D, H, W), dtype=torch.float32, device=x.device)
-    elif tuple(out.shape) != (B, Cout, D, H, W):
-        raise ValueError(f"out has shape {tuple(out.shape)}, expected {(B, Cout, D, H, W)}")
-    stride = 0
-    if shift is not None:
-        if shift.dim() != 2 or shift.shape[1] != Cout or shift.shape[0] not in (1, B):
-            raise ValueError(f"shift must be [1 or B, Cout]; got {tuple(shift.shape)}")
-        stride = 0 if shift.shape[0] == 1 else Cout
-    for r in (res1, res2):
-        if r is not None and tuple(r.shape) != (B, Cout, D, H, W):
-            raise ValueError("residual shape mismatch")
-    if bias is not None and bias.numel() != Cout:
-        raise ValueError("bias must have Cout entries")
+    D, H, W = _load_sides(load_mode, (Di, Hi, Wi))
+    out = _out(out, (B, Cout, D, H, W), x)
+    stride = _row_stride(shift, B, Cout, _SHIFT_MSG)
+    _residuals((B, Cout, D, H, W), res1, res2)
+    _entries(bias, Cout, "bias must have Cout entries")
     N.check(N.lib().ds_conv3d_direct(_p(out), _p(x.contiguous()), _p(w.contiguous()), _p(bias), _p(shift), stride, _p(res1),
                                      _p(res2), B, Cin, Cout, D, H, W,
                                      load_mode | (N.DS_PAD_CIRCULAR if circular else 0), _stream()), "ds_conv3d_direct")
@@ -397,22 +530,18 @@ def volume_stat_tiles(D, HW):
     return N.lib().ds_volume_stat_tiles(int(D), int(HW))
 
 
-def _slice_rows(shift, B, D, Cout, ws=None, pad=1):
-    """Per-slice rows of a per-sample time shift for the 2-D batch of all slices but the outermost `pad` on each end -> (rows,
-    buffer to give back to ws or None).  With a pool the expansion lands in a pool buffer (a captured loop must not allocate)."""
-    if shift is None:
-        return None, None
-    if shift.dim() != 2 or shift.shape[1] != Cout or shift.shape[0] not in (1, B):
-        raise ValueError(f"shift must be [1 or B, Cout]; got {tuple(shift.shape)}")
-    if shift.shape[0] == 1:
-        return shift, None
+def _slice_rows(shift, B, D, Cout, scratch, pad=1):
+    """Per-slice rows of a per-sample time shift for the 2-D batch of all slices but the outermost `pad` on each end.  The
+    expansion lands in a buffer of `scratch` (with a pool: a captured loop must not allocate)."""
+    if not _row_stride(shift, B, Cout, _SHIFT_MSG):
+        return shift
     DP = D + 2 * pad
     ns = B * DP
-    if ws is None:
-        return shift.repeat_interleave(DP, dim=0)[pad:ns - pad].contiguous(), None
-    buf = ws.take((B, DP, Cout), shift.device)
+    if scratch.ws is None:
+        return shift.repeat_interleave(DP, dim=0)[pad:ns - pad].contiguous()
+    buf = scratch.take((B, DP, Cout))
     buf.copy_(shift[:, None, :].expand(B, DP, Cout))
-    return buf.view(ns, Cout)[pad:ns - pad], buf
+    return buf.view(ns, Cout)[pad:ns - pad]
 
 
 def _depth_taps(s_in, s_out, packs, bias, rows, load_mode, circular, prenorm=None, tile_stats=None, in_amax=None):
@@ -465,34 +594,31 @@ def resblock3d_fused(h, tab1, packs1, bias1, shift, packs2, bias2, w2, b2, kind2
     B, C, D, H, W = h.shape
     if packs1[0].Cout != C or packs2[0].Cout != C:
         raise ValueError("resblock3d_fused keeps the channel count")
-    ns, dev = B * (D + 2), h.device
-
-    def take(shape):
-        return torch.empty(shape, dtype=torch.float32, device=dev) if ws is None else ws.take(shape, dev)
-    if out is None:
-        out = torch.empty_like(h)
-    s1 = take((ns, C, H, W))
+    ns, scratch = B * (D + 2), _Scratch(ws, h.device)
+    out = _out(out, (B, C, D, H, W), h)
+    _residuals((B, C, D, H, W), res2)
+    if tuple(tab1.shape) != (B, table_channels(C), 4):
+        raise ValueError(f"tab1 must be {(B, table_channels(C), 4)}; got {tuple(tab1.shape)}")
+    _affine(w2, b2, C, "resblock3d_fused")
+    s1 = scratch.take((ns, C, H, W))
     circ = 1 if circular else 0
     N.check(N.lib().ds_volume_to_slices_act(_p(s1), _p(h.contiguous()), _p(tab1), B, C, D, H * W, circ, _stream()),
             "ds_volume_to_slices_act")
-    s2 = take((ns, C, H, W))
+    s2 = scratch.take((ns, C, H, W))
     if not circular:
         s2[0].zero_()                                       # the outermost pad slices are never written by the launches
         s2[ns - 1].zero_()
-    ts = take((ns - 2, C, conv_tile_count(H, W), 4))
-    rows, rows_buf = _slice_rows(shift, B, D, C, ws)
+    ts = scratch.take((ns - 2, C, conv_tile_count(H, W), 4))
+    rows = _slice_rows(shift, B, D, C, scratch)
     _depth_taps(s1, s2, packs1, bias1, rows, N.DS_LOAD_PLAIN, bool(circular), tile_stats=ts, in_amax=NORMALISED)   # S1 = SiLU(norm1(h))
     if circular:
         N.check(N.lib().ds_wrap_pad_slices(_p(s2), B, C, D, H * W, _stream()), "ds_wrap_pad_slices")
-    tab2 = take((ns, table_channels(C), 4))
+    tab2 = scratch.take((ns, table_channels(C), 4))
     N.check(N.lib().ds_slice_tables(_p(tab2), _p(ts), _p(w2), _p(b2), B, C, D, ts.shape[2], D * H * W, float(eps), int(kind2),
                                     circ, _stream()), "ds_slice_tables")
     _depth_taps(s2, s1, packs2, bias2, None, N.DS_LOAD_PLAIN, bool(circular), prenorm=tab2)  # S1 is dead: reuse it for S3
     _from_slices(out, s1, h, res2, B, C, D, H * W, out_stats)
-    if ws is not None:
-        for t in (s1, s2, ts, tab2, rows_buf):
-            if t is not None:
-                ws.give(t)
+    scratch.give()
     return out
 
 
@@ -509,49 +635,24 @@ def conv3d_mfma(x, packs, bias=None, shift=None, res1=None, res2=None, load_mode
     require_device(x, "x")
     B, Cin, Din, Hi, Wi = x.shape
     Cout = packs[0].Cout
-    if load_mode == N.DS_LOAD_MAXPOOL2:
-        if Din % 2 or Hi % 2 or Wi % 2:
-            raise ValueError("pooling load needs an even input volume")
-        D, H, W, depth_mode = Din // 2, Hi // 2, Wi // 2, 1
-    elif load_mode == N.DS_LOAD_UPSAMPLE2:
-        D, H, W, depth_mode = 2 * Din, 2 * Hi, 2 * Wi, 2
-    else:
-        D, H, W, depth_mode = Din, Hi, Wi, 0
-    if out is None:
-        out = torch.empty((B, Cout, D, H, W), dtype=torch.float32, device=x.device)
-    elif tuple(out.shape) != (B, Cout, D, H, W):
-        raise ValueError(f"out has shape {tuple(out.shape)}, expected {(B, Cout, D, H, W)}")
-    for r in (res1, res2):
-        if r is not None and tuple(r.shape) != (B, Cout, D, H, W):
-            raise ValueError("residual shape mismatch")
+    D, H, W = _load_sides(load_mode, (Din, Hi, Wi))
+    depth_mode = {N.DS_LOAD_MAXPOOL2: 1, N.DS_LOAD_UPSAMPLE2: 2}.get(load_mode, 0)
+    out = _out(out, (B, Cout, D, H, W), x)
+    _residuals((B, Cout, D, H, W), res1, res2)
     P = len(packs) // 2
     if circular and P > D:
         raise ValueError(f"periodic padding of {P} slices needs a depth of at least {P}; got {D}")
-    ns = B * (D + 2 * P)
-
-    def take(shape):
-        return torch.empty(shape, dtype=torch.float32, device=x.device) if ws is None else ws.take(shape, x.device)
-    s_in = take((ns, Cin, Hi, Wi))
+    ns, scratch = B * (D + 2 * P), _Scratch(ws, x.device)
+    s_in = scratch.take((ns, Cin, Hi, Wi))
     N.check(N.lib().ds_volume_to_slices(_p(s_in), _p(x.contiguous()), B, Cin, D, Hi * Wi, depth_mode, 1 if circular else 0, P,
                                         _stream()), "ds_volume_to_slices")
-    s_out = take((ns, Cout, H, W))
-    rows, rows_buf = _slice_rows(shift, B, D, Cout, ws, pad=P)
-    am_buf = None
+    s_out = scratch.take((ns, Cout, H, W))
+    rows = _slice_rows(shift, B, D, Cout, scratch, pad=P)
     if in_amax is not NORMALISED:
-        if ws is None:
-            in_amax = absmax_rows(s_in)
-        else:
-            am_buf = ws.take((ns,), x.device)
-            in_amax = absmax_rows(s_in, out=amax_zero(am_buf.view(torch.int32)))
+        in_amax = absmax_rows(s_in, out=scratch.amax(ns))
     _depth_taps(s_in, s_out, packs, bias, rows, load_mode, circular, in_amax=in_amax)
     _from_slices(out, s_out, res1, res2, B, Cout, D, H * W, out_stats, pad=P)
-    if rows_buf is not None:
-        ws.give(rows_buf)
-    if am_buf is not None:
-        ws.give(am_buf)
-    if ws is not None:
-        ws.give(s_in)
-        ws.give(s_out)
+    scratch.give()
     return out
 
 
@@ -561,8 +662,7 @@ def avgpool3d(x, out=None):
     B, C, Di, Hi, Wi = x.shape
     if Di % 2 or Hi % 2 or Wi % 2:
         raise ValueError("avgpool3d needs even D, H, W")
-    if out is None:
-        out = torch.empty((B, C, Di // 2, Hi // 2, Wi // 2), dtype=torch.float32, device=x.device)
+    out = _out(out, (B, C, Di // 2, Hi // 2, Wi // 2), x)
     N.check(N.lib().ds_avgpool3d(_p(out, "out"), _p(x, "x"), B * C, Di // 2, Hi // 2, Wi // 2, _stream()), "ds_avgpool3d")
     return out
 
@@ -571,8 +671,7 @@ def upsample3d(x, out=None):
     """Nearest x2 upsampling of a volume [B, C, D, H, W]."""
     require_device(x, "x")
     B, C, Di, Hi, Wi = x.shape
-    if out is None:
-        out = torch.empty((B, C, 2 * Di, 2 * Hi, 2 * Wi), dtype=torch.float32, device=x.device)
+    out = _out(out, (B, C, 2 * Di, 2 * Hi, 2 * Wi), x)
     N.check(N.lib().ds_upsample3d(_p(out, "out"), _p(x, "x"), B * C, Di, Hi, Wi, _stream()), "ds_upsample3d")
     return out
 
@@ -588,18 +687,6 @@ def _factor(factor):
     return f
 
 
-def _film_args(film, B, C):
-    """(scale pointer, shift pointer, stride) of FiLM rows [1 or B, 2C] (embed_linear(te)), or (None, None, 0)."""
-    if film is None:
-        return None, None, 0
-    if film.dim() != 2 or film.shape[1] != 2 * C or film.shape[0] not in (1, B):
-        raise ValueError("film must be [1 or B, 2C]")
-    require_device(film, "film")
-    if not film.is_contiguous():
-        raise ValueError("film must be contiguous")
-    return film.data_ptr(), film.data_ptr() + 4 * C, (0 if film.shape[0] == 1 else 2 * C)
-
-
 def gnorm1_apply_poolf(x, stats, w, b, kind, factor, film=None, out=None):
     """gnorm1_apply followed by AvgPool2d(factor) for any integer factor >= 1 (floor output size, as torch):
     x [B, C, H, W] -> [B, C, H // f, W // f].  kind 2 pools the raw x."""
@@ -608,11 +695,9 @@ def gnorm1_apply_poolf(x, stats, w, b, kind, factor, film=None, out=None):
     B, C, H, W = x.shape
     if f > min(H, W):
         raise ValueError(f"pooling factor {f} exceeds the field {H}x{W}")
-    if out is None:
-        out = torch.empty((B, C, H // f, W // f), dtype=torch.float32, device=x.device)
-    elif tuple(out.shape) != (B, C, H // f, W // f):
-        raise ValueError(f"out has shape {tuple(out.shape)}, expected {(B, C, H // f, W // f)}")
+    out = _out(out, (B, C, H // f, W // f), x)
     f1, f2, stride = _film_args(film, B, C)
+    _gnorm1_inputs(stats, w, b, B, C, "gnorm1_apply_poolf")
     N.check(N.lib().ds_gnorm1_apply_poolf(_p(out), _p(x), _p(stats), _p(w), _p(b), f1, f2, stride, B, C, H, W, int(kind), f,
                                           _stream()), "ds_gnorm1_apply_poolf")
     return out
@@ -631,10 +716,7 @@ def avgpool_f(x, factor, out=None):
     if f > min(Di, Hi, Wi):
         raise ValueError(f"pooling factor {f} exceeds the volume {Di}x{Hi}x{Wi}")
     shape = (B, C, Di // f, Hi // f, Wi // f)
-    if out is None:
-        out = torch.empty(shape, dtype=torch.float32, device=x.device)
-    elif tuple(out.shape) != shape:
-        raise ValueError(f"out has shape {tuple(out.shape)}, expected {shape}")
+    out = _out(out, shape, x)
     N.check(N.lib().ds_avgpool3d_f(_p(out, "out"), _p(x, "x"), B * C, Di, Hi, Wi, f, _stream()), "ds_avgpool3d_f")
     return out
 
@@ -650,10 +732,7 @@ def upsample_f(x, factor, out=None):
     B, C = x.shape[:2]
     Di, Hi, Wi = (x.shape[2:] if vol else (1,) + tuple(x.shape[2:]))
     shape = (B, C) + ((f * Di,) if vol else ()) + (f * Hi, f * Wi)
-    if out is None:
-        out = torch.empty(shape, dtype=torch.float32, device=x.device)
-    elif tuple(out.shape) != shape:
-        raise ValueError(f"out has shape {tuple(out.shape)}, expected {shape}")
+    out = _out(out, shape, x)
     N.check(N.lib().ds_upsample_f(_p(out, "out"), _p(x, "x"), B * C, Di, Hi, Wi, f, 1 if vol else 0, _stream()),
             "ds_upsample_f")
     return out
@@ -673,10 +752,7 @@ def maxpool_f(x, factor, out=None):
         raise ValueError(f"pooling factor {f} exceeds the {'volume' if vol else 'field'} {'x'.join(map(str, sides))}")
     Di, Hi, Wi = sides if vol else (1,) + sides
     shape = (B, C) + tuple(v // f for v in sides)
-    if out is None:
-        out = torch.empty(shape, dtype=torch.float32, device=x.device)
-    elif tuple(out.shape) != shape:
-        raise ValueError(f"out has shape {tuple(out.shape)}, expected {shape}")
+    out = _out(out, shape, x)
     N.check(N.lib().ds_maxpool_f(_p(out, "out"), _p(x, "x"), B * C, Di, Hi, Wi, f, 1 if vol else 0, _stream()), "ds_maxpool_f")
     return out
 
@@ -702,11 +778,10 @@ def cornerpool_f(x, factor, te=None, out=None, out_amax=None):
     if Bx not in (1, B) or (te is not None and te.shape[0] not in (1, B)):
         raise ValueError(f"x {tuple(x.shape)} and te {None if te is None else tuple(te.shape)} must have batch 1 or {B}")
     shape = (B, C) + tuple(v // f for v in sides)
-    if out is not None and tuple(out.shape) != shape:
-        raise ValueError(f"out has shape {tuple(out.shape)}, expected {shape}")
+    if out is not None:
+        _out(out, shape, x)
     require_device(x, "x")
-    if out is None:
-        out = torch.empty(shape, dtype=torch.float32, device=x.device)
+    out = _out(out, shape, x)
     Di, Hi, Wi = sides if vol else (1,) + sides
     N.check(N.lib().ds_cornerpool_f(_p(out, "out"), _p(x, "x"), _p(te, "te"), _pi(out_amax, B, "out_amax"), B, C, Di, Hi, Wi, f,
                                     1 if vol else 0, Bx, 1 if te is None else te.shape[0], _stream()), "ds_cornerpool_f")
@@ -717,13 +792,8 @@ def gnorm1_stats(x, kind, eps=1e-5, stats=None, workspace=None):
     """Per-sample (mean, rstd) [kind 0] or (0, rms denominator) [kind 1] over (C, H, W)."""
     B, C = x.shape[0], x.shape[1]
     HW = x.numel() // max(B * C, 1)
-    if stats is None:
-        stats = torch.empty((B, 2), dtype=torch.float32, device=x.device)
-    need = N.lib().ds_gnorm1_workspace_bytes(B)
-    if workspace is None:
-        workspace = torch.empty(need // 4, dtype=torch.float32, device=x.device)
-    elif workspace.numel() * 4 < need:
-        raise ValueError("gnorm1 workspace too small")
+    workspace = _workspace(workspace, N.lib().ds_gnorm1_workspace_bytes(B), x, "gnorm1 workspace too small")
+    stats = _out(stats, (B, 2), x, _STATS_MSG)
     N.check(N.lib().ds_gnorm1_stats(_p(stats), _p(workspace), _p(x), B, C, HW, float(eps), int(kind), _stream()),
             "ds_gnorm1_stats")
     return stats
@@ -734,16 +804,9 @@ def gnorm1_apply(x, stats, w, b, kind, pool=False, film=None, out=None):
     kind 2: identity; then optional 2x2 average pooling.  film: [1 or B, 2C] rows of embed_linear(te)."""
     B, C, H, W = x.shape
     Ho, Wo = (H // 2, W // 2) if pool else (H, W)
-    if out is None:
-        out = torch.empty((B, C, Ho, Wo), dtype=torch.float32, device=x.device)
-    f1 = f2 = None
-    stride = 0
-    if film is not None:
-        if film.dim() != 2 or film.shape[1] != 2 * C or film.shape[0] not in (1, B):
-            raise ValueError("film must be [1 or B, 2C]")
-        require_device(film, "film")
-        stride = 0 if film.shape[0] == 1 else 2 * C
-        f1, f2 = film.data_ptr(), film.data_ptr() + 4 * C
+    f1, f2, stride = _film_args(film, B, C)
+    _gnorm1_inputs(stats, w, b, B, C, "gnorm1_apply")
+    out = _out(out, (B, C, Ho, Wo), x)
     N.check(N.lib().ds_gnorm1_apply(_p(out), _p(x), _p(stats), _p(w), _p(b), f1, f2, stride, B, C, H, W, int(kind),
                                     1 if pool else 0, _stream()), "ds_gnorm1_apply")
     return out
@@ -755,30 +818,14 @@ def _groupnorm_dims(x, G, what):
     if x.dim() < 3:
         raise ValueError(f"{what}: x must be [B, C, *spatial]")
     B, C = x.shape[0], x.shape[1]
-    G = int(G)
-    if G < 1 or C % G:
-        raise ValueError(f"{what}: C={C} is not a multiple of num_groups={G}")
-    return B, C, G, x.numel() // max(B * C, 1)
-
-
-def _affine(w, b, C, what):
-    for t, name in ((w, "weight"), (b, "bias")):
-        if t is not None and t.numel() != C:
-            raise ValueError(f"{what}: norm {name} must have C={C} entries")
+    return B, C, _groups(C, G, what), x.numel() // max(B * C, 1)
 
 
 def groupnorm_stats(x, G, eps=1e-6, stats=None, workspace=None):
     """(mean, rstd) [B, G, 2] of GroupNorm(G, C) over x [B, C, *spatial] (biased variance, fp64 accumulation)."""
     B, C, G, n = _groupnorm_dims(x, G, "groupnorm_stats")
-    if stats is None:
-        stats = torch.empty((B, G, 2), dtype=torch.float32, device=x.device)
-    elif tuple(stats.shape) != (B, G, 2):
-        raise ValueError(f"stats must be {(B, G, 2)}")
-    need = N.lib().ds_gnorm1_workspace_bytes(B * G)
-    if workspace is None:
-        workspace = torch.empty(need // 4, dtype=torch.float32, device=x.device)
-    elif workspace.numel() * 4 < need:
-        raise ValueError("groupnorm workspace too small")
+    stats = _out(stats, (B, G, 2), x, _STATS_MSG)
+    workspace = _workspace(workspace, N.lib().ds_gnorm1_workspace_bytes(B * G), x, "groupnorm workspace too small")
     N.check(N.lib().ds_groupnorm_stats(_p(stats, "stats"), _p(workspace, "workspace"), _p(x, "x"), B, C, G, n, float(eps), _stream()),
             "ds_groupnorm_stats")
     return stats
@@ -791,10 +838,7 @@ def groupnorm_apply(x, stats, w, b, G, act=False, out=None, out_amax=None):
     if tuple(stats.shape) != (B, G, 2):
         raise ValueError(f"stats must be {(B, G, 2)}; got {tuple(stats.shape)}")
     _affine(w, b, C, "groupnorm_apply")
-    if out is None:
-        out = torch.empty_like(x)
-    elif tuple(out.shape) != tuple(x.shape):
-        raise ValueError("groupnorm_apply: out must have x's shape")
+    out = _out(out, x.shape, x, "groupnorm_apply: out must have x's shape")
     N.check(N.lib().ds_groupnorm_apply(_p(out, "out"), _p(x, "x"), _p(stats, "stats"), _p(w, "weight"), _p(b, "bias"), B, C, G, n,
                                        1 if act else 0, _pi(out_amax, B, "out_amax"), _stream()), "ds_groupnorm_apply")
     return out
@@ -805,13 +849,8 @@ def groupnorm_stats_tiles(tile_stats, G, count, eps=1e-6, stats=None):
     a pass over the tensor; count: positions per channel."""
     require_device(tile_stats, "tile_stats")
     B, C, nt, _ = tile_stats.shape
-    G = int(G)
-    if G < 1 or C % G:
-        raise ValueError(f"groupnorm_stats_tiles: C={C} is not a multiple of num_groups={G}")
-    if stats is None:
-        stats = torch.empty((B, G, 2), dtype=torch.float32, device=tile_stats.device)
-    elif tuple(stats.shape) != (B, G, 2):
-        raise ValueError(f"stats must be {(B, G, 2)}")
+    G = _groups(C, G, "groupnorm_stats_tiles")
+    stats = _out(stats, (B, G, 2), tile_stats, _STATS_MSG)
     N.check(N.lib().ds_groupnorm_stats_tiles(_p(stats, "stats"), _p(tile_stats, "tile_stats"), B, C, G, nt, int(count), float(eps),
                                              _stream()), "ds_groupnorm_stats_tiles")
     return stats
@@ -831,13 +870,9 @@ def groupnorm_table(w, b, G, count, tile_stats=None, stats=None, eps=1e-6, out=N
         if w is None or stats.dim() != 3 or tuple(stats.shape[1:]) != (G, 2):
             raise ValueError("groupnorm_table: stats must be [B, G, 2] and the weight gives the channel count")
         B, C, nt = stats.shape[0], w.numel(), 0
-    if G < 1 or C % G:
-        raise ValueError(f"groupnorm_table: C={C} is not a multiple of num_groups={G}")
+    G = _groups(C, G, "groupnorm_table")
     _affine(w, b, C, "groupnorm_table")
-    if out is None:
-        out = torch.empty((B, table_channels(C), 4), dtype=torch.float32, device=(tile_stats if stats is None else stats).device)
-    elif tuple(out.shape) != (B, table_channels(C), 4):
-        raise ValueError(f"table must be {(B, table_channels(C), 4)}")
+    out = _out(out, (B, table_channels(C), 4), tile_stats if stats is None else stats, _TABLE_MSG)
     N.check(N.lib().ds_groupnorm_table(_p(out, "table"), _p(tile_stats, "tile_stats"), _p(stats, "stats"), _p(w, "weight"), _p(b, "bias"),
                                        B, C, G, nt, int(count), float(eps), _stream()), "ds_groupnorm_table")
     return out
@@ -846,10 +881,10 @@ def groupnorm_table(w, b, G, count, tile_stats=None, stats=None, eps=1e-6, out=N
 def tanh(x, out=None):
     """tanh(x), any shape."""
     require_device(x, "x")
-    out = torch.empty_like(x) if out is None else out
     if x.numel() >= 1 << 31:
         raise ValueError("tanh: at most 2^31 - 1 elements")
-    N.check(N.lib().ds_add_act(_p(out, "out"), _p(x, "x"), None, 0, 1, x.numel(), 3, _stream()), "ds_add_act")
+    out, n = _out_flat(out, x)
+    N.check(N.lib().ds_add_act(_p(out, "out"), _p(x, "x"), None, 0, 1, n, 3, _stream()), "ds_add_act")
     return out
 
 
@@ -857,19 +892,22 @@ def concat2(a, b, out=None):
     """cat([a, b], dim=1) for [B, C, H, W] tensors."""
     B = a.shape[0]
     na, nb = a.numel() // max(B, 1), b.numel() // max(B, 1)
-    if out is None:
-        out = torch.empty((B, a.shape[1] + b.shape[1]) + tuple(a.shape[2:]), dtype=torch.float32, device=a.device)
+    # the kernel appends nb floats of b to na floats of a per sample: the same batch and the same spatial sides, axes of length
+    # one aside (PUNetGCond hands in [B, C, 1, H, W] fields next to a [B, C, H, W] input)
+    if a.dim() < 2 or b.dim() < 2 or b.shape[0] != B or [n for n in b.shape[2:] if n != 1] != [n for n in a.shape[2:] if n != 1]:
+        raise ValueError(f"concat2: a {tuple(a.shape)} and b {tuple(b.shape)} must agree in all but the channel axis")
+    out = _out(out, (B, a.shape[1] + b.shape[1]) + tuple(a.shape[2:]), a)
     N.check(N.lib().ds_concat2(_p(out), _p(a), _p(b), B, na, nb, _stream()), "ds_concat2")
     return out
 
 
 def add_act(a, add=None, act=0, out=None):
     M, Nn = a.shape
-    out = torch.empty_like(a) if out is None else out
     rows = 0
     if add is not None:
         add = add.reshape(-1, Nn)
         rows = add.shape[0]
+    out, _ = _out_flat(out, a)
     N.check(N.lib().ds_add_act(_p(out), _p(a), _p(add), rows, M, Nn, int(act), _stream()), "ds_add_act")
     return out
 
@@ -989,10 +1027,8 @@ def conv_direct(x, w, bias=None, circular=False, out=None):
     Cout = w.shape[0]
     if tuple(w.shape) != (Cout, Cin, 3, 3):
         raise ValueError("conv_direct: weight must be [Cout, Cin, 3, 3]")
-    if out is None:
-        out = torch.empty((B, Cout, H, W), dtype=torch.float32, device=x.device)
-    elif tuple(out.shape) != (B, Cout, H, W):
-        raise ValueError(f"out has shape {tuple(out.shape)}, expected {(B, Cout, H, W)}")
+    out = _out(out, (B, Cout, H, W), x)
+    _entries(bias, Cout, "bias must have Cout entries")
     N.check(N.lib().ds_conv2d_direct(_p(out), _p(x), _p(w), _p(bias), B, Cin, Cout, H, W, 1 if circular else 0,
                                      _stream()), "ds_conv2d_direct")
     return out
@@ -1028,14 +1064,9 @@ def conv_s2(x, pw, bias=None, res1=None, in_amax=None, out_amax=None, out=None):
         raise ValueError(f"conv_s2: x must be [B, {pw.Cin}, H, W] and the weight 3x3; got {tuple(x.shape)}")
     B, Cin, Hin, Win = x.shape
     H, W = _s2_sides((Hin, Win), "conv_s2")
-    if out is None:
-        out = torch.empty((B, pw.Cout, H, W), dtype=torch.float32, device=x.device)
-    elif tuple(out.shape) != (B, pw.Cout, H, W):
-        raise ValueError(f"out has shape {tuple(out.shape)}, expected {(B, pw.Cout, H, W)}")
-    if res1 is not None and tuple(res1.shape) != tuple(out.shape):
-        raise ValueError("residual shape mismatch")
-    if bias is not None and bias.numel() != pw.Cout:
-        raise ValueError("bias must have Cout entries")
+    out = _out(out, (B, pw.Cout, H, W), x)
+    _residuals((B, pw.Cout, H, W), res1)
+    _entries(bias, pw.Cout, "bias must have Cout entries")
     x = x.contiguous()
     if pw.kind == "fp16x3":
         pin = _in_amax(x, in_amax, B, raw=True)
@@ -1077,14 +1108,9 @@ def conv3d_s2(x, packs, bias=None, res1=None, out=None, ws=None):
         raise ValueError(f"conv3d_s2: x must be [B, {Cin}, D, H, W]; got {tuple(x.shape)}")
     B, _, Din, Hin, Win = x.shape
     D, H, W = _s2_sides((Din, Hin, Win), "conv3d_s2")
-    if out is None:
-        out = torch.empty((B, Cout, D, H, W), dtype=torch.float32, device=x.device)
-    elif tuple(out.shape) != (B, Cout, D, H, W):
-        raise ValueError(f"out has shape {tuple(out.shape)}, expected {(B, Cout, D, H, W)}")
-    if res1 is not None and tuple(res1.shape) != tuple(out.shape):
-        raise ValueError("residual shape mismatch")
-    if bias is not None and bias.numel() != Cout:
-        raise ValueError("bias must have Cout entries")
+    out = _out(out, (B, Cout, D, H, W), x)
+    _residuals((B, Cout, D, H, W), res1)
+    _entries(bias, Cout, "bias must have Cout entries")
     x = x.contiguous()
     if direct:
         if packs.kind != "direct":
@@ -1092,29 +1118,18 @@ def conv3d_s2(x, packs, bias=None, res1=None, out=None, ws=None):
         N.check(N.lib().ds_conv3d_s2_direct(_p(out, "out"), _p(x), _p(packs.data), _p(bias), _p(res1), B, Cin, Cout, Din, Hin, Win,
                                             _stream()), "ds_conv3d_s2_direct")
         return out
-
-    def take(shape):
-        return torch.empty(shape, dtype=torch.float32, device=x.device) if ws is None else ws.take(shape, x.device)
-    ns = B * (Din + 2)
-    s_in = take((ns, Cin, Hin, Win))
+    ns, scratch = B * (Din + 2), _Scratch(ws, x.device)
+    s_in = scratch.take((ns, Cin, Hin, Win))
     N.check(N.lib().ds_volume_to_slices(_p(s_in), _p(x), B, Cin, Din, Hin * Win, 0, 0, 1, _stream()), "ds_volume_to_slices")
-    if ws is None:
-        am = absmax_rows(s_in)
-        am_buf = None
-    else:
-        am_buf = ws.take((ns,), x.device)
-        am = absmax_rows(s_in, out=amax_zero(am_buf.view(torch.int32)))
-    s_out = take((B * D, Cout, H, W))
+    am = absmax_rows(s_in, out=scratch.amax(ns))
+    s_out = scratch.take((B * D, Cout, H, W))
     for kz in range(3):                                  # slice 1 + 2d + kz of the sample's D + 2
         pk = packs[kz]
         N.check(N.lib().ds_conv2d_s2_h3(_p(s_out), s_in[1 + kz].data_ptr(), _p(pk.data), int(pk.wshift), _p(bias) if kz == 0 else None,
                                         None if kz == 0 else _p(s_out), B * D, Cin, Cout, Hin, Win, D, Din + 2, 2,
                                         am.data_ptr() + 4 * (1 + kz), None, _stream()), "ds_conv2d_s2_h3")
     _from_slices(out, s_out, res1, None, B, Cout, D, H * W, pad=0)
-    if ws is not None:
-        for t in (s_in, s_out, am_buf):
-            if t is not None:
-                ws.give(t)
+    scratch.give()
     return out
 
 
@@ -1132,10 +1147,7 @@ def posterior_sample(moments, eps=None, clamp=None, out=None):
     B, Z = moments.shape[0], moments.shape[1] // 2
     shape = (B, Z) + tuple(moments.shape[2:])
     per = moments.numel() // max(2 * B, 1)
-    if out is None:
-        out = torch.empty(shape, dtype=torch.float32, device=moments.device)
-    elif tuple(out.shape) != shape:
-        raise ValueError(f"out has shape {tuple(out.shape)}, expected {shape}")
+    out = _out(out, shape, moments)
     lo, hi, has = 0.0, 0.0, 0
     if clamp is not None:
         lo, hi = (float(v) for v in clamp)
@@ -1214,10 +1226,8 @@ def inorm_table(tile_stats, w, b, kind, count, eps=1e-5, out=None):
     """PUNetG norm table [B, ceil16(C), 4] from a convolution's tile statistics [B, C, ntiles, 4]: rows (M, A, C, 2^-k), k the
     sample's activation exponent for the consuming loader."""
     B, C, nt, _ = tile_stats.shape
-    if out is None:
-        out = torch.empty((B, table_channels(C), 4), dtype=torch.float32, device=tile_stats.device)
-    elif tuple(out.shape) != (B, table_channels(C), 4):
-        raise ValueError(f"table must be {(B, table_channels(C), 4)}")
+    out = _out(out, (B, table_channels(C), 4), tile_stats, _TABLE_MSG)
+    _affine(w, b, C, "inorm_table")
     N.check(N.lib().ds_inorm_table(_p(out), _p(tile_stats), _p(w), _p(b), B, C, nt, int(count), float(eps), int(kind),
                                    _stream()), "ds_inorm_table")
     return out
@@ -1229,18 +1239,9 @@ def gnorm1_table(stats_a, w, b, kind, count, stats_b=None, film=None, eps=1e-5, 
     B, Ca, nta, _ = stats_a.shape
     Cb, ntb = (0, 0) if stats_b is None else (stats_b.shape[1], stats_b.shape[2])
     C = Ca + Cb
-    if out is None:
-        out = torch.empty((B, table_channels(C), 4), dtype=torch.float32, device=stats_a.device)
-    elif tuple(out.shape) != (B, table_channels(C), 4):
-        raise ValueError(f"table must be {(B, table_channels(C), 4)}")
-    f1 = f2 = None
-    stride = 0
-    if film is not None:
-        if film.dim() != 2 or film.shape[1] != 2 * C or film.shape[0] not in (1, B):
-            raise ValueError("film must be [1 or B, 2C]")
-        require_device(film, "film")
-        stride = 0 if film.shape[0] == 1 else 2 * C
-        f1, f2 = film.data_ptr(), film.data_ptr() + 4 * C
+    out = _out(out, (B, table_channels(C), 4), stats_a, _TABLE_MSG)
+    f1, f2, stride = _film_args(film, B, C)
+    _affine(w, b, C, "gnorm1_table")
     N.check(N.lib().ds_gnorm1_table(_p(out), _p(stats_a), Ca, nta, _p(stats_b), Cb, ntb, _p(w), _p(b), f1, f2, stride,
                                     B, int(count), float(eps), int(kind), _stream()), "ds_gnorm1_table")
     return out
@@ -1251,10 +1252,7 @@ def gnorm1_stats_tiles(stats_a, kind, count, stats_b=None, eps=1e-5, stats=None)
     require_device(stats_a, "stats_a")
     B, Ca, nta, _ = stats_a.shape
     Cb, ntb = (0, 0) if stats_b is None else (stats_b.shape[1], stats_b.shape[2])
-    if stats is None:
-        stats = torch.empty((B, 2), dtype=torch.float32, device=stats_a.device)
-    elif tuple(stats.shape) != (B, 2):
-        raise ValueError(f"stats must be {(B, 2)}")
+    stats = _out(stats, (B, 2), stats_a, _STATS_MSG)
     N.check(N.lib().ds_gnorm1_stats_tiles(_p(stats), _p(stats_a), Ca, nta, _p(stats_b), Cb, ntb, B, int(count), float(eps),
                                           int(kind), _stream()), "ds_gnorm1_stats_tiles")
     return stats
@@ -1271,39 +1269,23 @@ def conv2d(x, w_packed, Cout, ks, bias=None, shift=None, res1=None, res2=None,
     per-sample max |out| for the next raw-input launch; amax_split (fp16x3 1x1 only): out_amax is [2, B] and channels >=
     amax_split report to its second row (the attention in-projection: q, k | v)."""
     B, Cin, Hin, Win = x.shape
+    H, W = _load_sides(load_mode, (Hin, Win))
     if load_mode in (N.DS_LOAD_MAXPOOL2, N.DS_LOAD_AVGPOOL2):
-        if Hin % 2 or Win % 2:
-            raise ValueError("pooling load needs even input H, W")
         if (load_mode == N.DS_LOAD_AVGPOOL2) != (kind == "fp16x3" and ks == 1):
             raise ValueError("load modes: AVGPOOL2 is for the fp16x3 1x1 kernel, MAXPOOL2 for the others")
-        H, W = Hin // 2, Win // 2
-    elif load_mode == N.DS_LOAD_UPSAMPLE2:
-        H, W = Hin * 2, Win * 2
-    else:
-        H, W = Hin, Win
-    if out is None:
-        out = torch.empty((B, Cout, H, W), dtype=torch.float32, device=x.device)
-    elif tuple(out.shape) != (B, Cout, H, W):
-        raise ValueError(f"out has shape {tuple(out.shape)}, expected {(B, Cout, H, W)}")
+    out = _out(out, (B, Cout, H, W), x)
     expect = {"bf16x6": lambda: N.lib().ds_conv2d_x6_packed_bytes(Cout, Cin) // 4,
               "fp16x3": lambda: (N.lib().ds_conv2d_h3_packed_bytes if ks == 3 else
                                  N.lib().ds_conv1x1_h3_packed_bytes)(Cout, Cin) // 4,
               "fp32": lambda: N.lib().ds_conv2d_packed_floats(Cout, Cin, ks)}[kind]()
     if w_packed.numel() != expect or (kind == "bf16x6" and ks != 3) or ks not in (1, 3):
         raise ValueError("packed weight size does not match (Cout, Cin, ks)")
-    stride = 0
-    if shift is not None:
-        if shift.dim() != 2 or shift.shape[1] != Cout or shift.shape[0] not in (1, B):
-            raise ValueError(f"shift must be [1 or B, Cout]; got {tuple(shift.shape)}")
-        stride = 0 if shift.shape[0] == 1 else Cout
+    stride = _row_stride(shift, B, Cout, _SHIFT_MSG)
     if res1_upsampled:
         if kind != "fp16x3" or ks != 3 or res1 is None or H % 2 or W % 2 or tuple(res1.shape) != (B, Cout, H // 2, W // 2):
             raise ValueError("res1_upsampled: fp16x3 3x3 convolution with res1 of shape [B, Cout, H/2, W/2]")
-    for r in ((res2,) if res1_upsampled else (res1, res2)):
-        if r is not None and tuple(r.shape) != (B, Cout, H, W):
-            raise ValueError("residual shape mismatch")
-    if bias is not None and bias.numel() != Cout:
-        raise ValueError("bias must have Cout entries")
+    _residuals((B, Cout, H, W), None if res1_upsampled else res1, res2)
+    _entries(bias, Cout, "bias must have Cout entries")
     if (prenorm is not None or tile_stats is not None) and kind != "fp16x3":
         raise ValueError("prenorm / tile_stats are features of the fp16x3 kernels")
     pin = pout = None
@@ -1318,8 +1300,7 @@ def conv2d(x, w_packed, Cout, ks, bias=None, shift=None, res1=None, res2=None,
         raise NotImplementedError("periodic padding is implemented in the fp16x3 convolution only")
     if prenorm is not None and (ks != 3 or tuple(prenorm.shape) != (B, table_channels(Cin), 4)):
         raise ValueError(f"prenorm must be [B, ceil16(Cin), 4] on a 3x3 convolution; got {tuple(prenorm.shape)}")
-    if tile_stats is not None and tuple(tile_stats.shape) != (B, Cout, conv_tile_count(H, W), 4):
-        raise ValueError(f"tile_stats must be {(B, Cout, conv_tile_count(H, W), 4)}; got {tuple(tile_stats.shape)}")
+    _tile_stats(tile_stats, B, Cout, H, W, got=True)
     tap = 0
     if tap_offset is not None and tuple(tap_offset) != (0, 0):
         oy, ox = (int(v) for v in tap_offset)
@@ -1367,11 +1348,7 @@ def inorm_silu_images(x, w, b, kind, eps=1e-5, out=None):
     """inorm_silu with the result written as the consuming convolution's pre-split fp16 hi / lo images (conv_img)."""
     require_device(x, "x")
     B, C, H, W = x.shape
-    n = conv_images_floats(B, C, H, W)
-    if out is None:
-        out = torch.empty(n, dtype=torch.float32, device=x.device)
-    elif out.numel() != n:
-        raise ValueError("images buffer size does not match x")
+    out = _images(out, B, C, H, W, "images buffer size does not match x", like=x)
     if w is not None and (w.numel() != C or b.numel() != C):
         raise ValueError("norm affine parameters must have C entries")
     N.check(N.lib().ds_inorm_silu_images(_p(out), _p(x), _p(w), _p(b), B, C, H, W, float(eps), int(kind), _stream()),
@@ -1387,24 +1364,14 @@ def conv_img(images, pw, B, Cin, H, W, bias=None, shift=None, res1=None, res2=No
     if pw.kind != "fp16x3" or pw.ks != 3 or pw.subs is not None:
         raise ValueError("conv_img: a 3x3 fp16x3 packing")
     Cout = pw.Cout
-    if images.numel() != conv_images_floats(B, Cin, H, W):
-        raise ValueError("images size does not match (B, Cin, H, W)")
-    if out is None:
-        out = torch.empty((B, Cout, H, W), dtype=torch.float32, device=images.device)
-    elif tuple(out.shape) != (B, Cout, H, W):
-        raise ValueError(f"out has shape {tuple(out.shape)}, expected {(B, Cout, H, W)}")
-    stride = 0
-    if shift is not None:
-        if shift.dim() != 2 or shift.shape[1] != Cout or shift.shape[0] not in (1, B):
-            raise ValueError(f"shift must be [1 or B, Cout]; got {tuple(shift.shape)}")
-        stride = 0 if shift.shape[0] == 1 else Cout
+    _images(images, B, Cin, H, W, "images size does not match (B, Cin, H, W)")
+    out = _out(out, (B, Cout, H, W), images)
+    stride = _row_stride(shift, B, Cout, _SHIFT_MSG)
     if res1_upsampled and (res1 is None or H % 2 or W % 2 or tuple(res1.shape) != (B, Cout, H // 2, W // 2)):
         raise ValueError("res1_upsampled: res1 of shape [B, Cout, H/2, W/2]")
-    for r in ((res2,) if res1_upsampled else (res1, res2)):
-        if r is not None and tuple(r.shape) != (B, Cout, H, W):
-            raise ValueError("residual shape mismatch")
-    if tile_stats is not None and tuple(tile_stats.shape) != (B, Cout, conv_tile_count(H, W), 4):
-        raise ValueError(f"tile_stats must be {(B, Cout, conv_tile_count(H, W), 4)}")
+    _residuals((B, Cout, H, W), None if res1_upsampled else res1, res2)
+    _tile_stats(tile_stats, B, Cout, H, W)
+    _entries(bias, Cout, "bias must have Cout entries")
     N.check(N.lib().ds_conv2d_h3_img(_p(out), _p(images), _p(pw.data), int(pw.wshift), _p(bias), _p(shift), stride, _p(res1),
                                      _p(res2), B, Cin, Cout, H, W, N.DS_RES1_UPSAMPLED if res1_upsampled else 0,
                                      _p(tile_stats), _pi(out_amax, B, "out_amax"), _stream()), "ds_conv2d_h3_img")
@@ -1419,11 +1386,7 @@ def table_apply_images(x, table, out=None):
     B, C, H, W = x.shape
     if tuple(table.shape) != (B, table_channels(C), 4):
         raise ValueError(f"table must be {(B, table_channels(C), 4)}; got {tuple(table.shape)}")
-    n = conv_images_floats(B, C, H, W)
-    if out is None:
-        out = torch.empty(n, dtype=torch.float32, device=x.device)
-    elif out.numel() != n:
-        raise ValueError("images buffer size does not match x")
+    out = _images(out, B, C, H, W, "images buffer size does not match x", like=x)
     N.check(N.lib().ds_table_apply_images(_p(out), _p(x), _p(table), B, C, H, W, _stream()), "ds_table_apply_images")
     return out
 
@@ -1442,22 +1405,12 @@ def conv_up_img(images, pw, B, Cin, Hl, Wl, bias=None, shift=None, res1=None, re
     if not conv_up_img_supported(pw, Hl, Wl):
         raise ValueError("conv_up_img: a 3x3 fp16x3 packing with parity kernels and an input of whole 8x32 / 16x16 tiles")
     Cout, H, W = pw.Cout, 2 * Hl, 2 * Wl
-    if images.numel() != conv_images_floats(B, Cin, Hl, Wl):
-        raise ValueError("images size does not match (B, Cin, Hl, Wl)")
-    if out is None:
-        out = torch.empty((B, Cout, H, W), dtype=torch.float32, device=images.device)
-    elif tuple(out.shape) != (B, Cout, H, W):
-        raise ValueError(f"out has shape {tuple(out.shape)}, expected {(B, Cout, H, W)}")
-    stride = 0
-    if shift is not None:
-        if shift.dim() != 2 or shift.shape[1] != Cout or shift.shape[0] not in (1, B):
-            raise ValueError(f"shift must be [1 or B, Cout]; got {tuple(shift.shape)}")
-        stride = 0 if shift.shape[0] == 1 else Cout
-    for r in (res1, res2):
-        if r is not None and tuple(r.shape) != (B, Cout, H, W):
-            raise ValueError("residual shape mismatch")
-    if tile_stats is not None and tuple(tile_stats.shape) != (B, Cout, conv_tile_count(H, W), 4):
-        raise ValueError(f"tile_stats must be {(B, Cout, conv_tile_count(H, W), 4)}")
+    _images(images, B, Cin, Hl, Wl, "images size does not match (B, Cin, Hl, Wl)")
+    out = _out(out, (B, Cout, H, W), images)
+    stride = _row_stride(shift, B, Cout, _SHIFT_MSG)
+    _residuals((B, Cout, H, W), res1, res2)
+    _tile_stats(tile_stats, B, Cout, H, W)
+    _entries(bias, Cout, "bias must have Cout entries")
     N.check(N.lib().ds_conv2d_h3_up_img(_p(out), _p(images), _p(pw.up), int(pw.up_wshift), _p(bias), _p(shift), stride, _p(res1),
                                         _p(res2), B, Cin, Cout, Hl, Wl, _p(tile_stats), _pi(out_amax, B, "out_amax"), _stream()),
             "ds_conv2d_h3_up_img")
@@ -1471,19 +1424,9 @@ def gnorm1_apply_images(x, stats, w, b, kind, pool=False, film=None, out=None):
     if pool and (H % 2 or W % 2):
         raise ValueError("pooling needs even H, W")
     Ho, Wo = (H // 2, W // 2) if pool else (H, W)
-    n = conv_images_floats(B, C, Ho, Wo)
-    if out is None:
-        out = torch.empty(n, dtype=torch.float32, device=x.device)
-    elif out.numel() != n:
-        raise ValueError("images buffer size does not match x")
-    f1 = f2 = None
-    stride = 0
-    if film is not None:
-        if film.dim() != 2 or film.shape[1] != 2 * C or film.shape[0] not in (1, B):
-            raise ValueError("film must be [1 or B, 2C]")
-        require_device(film, "film")
-        stride = 0 if film.shape[0] == 1 else 2 * C
-        f1, f2 = film.data_ptr(), film.data_ptr() + 4 * C
+    out = _images(out, B, C, Ho, Wo, "images buffer size does not match x", like=x)
+    f1, f2, stride = _film_args(film, B, C)
+    _gnorm1_inputs(stats, w, b, B, C, "gnorm1_apply_images")
     N.check(N.lib().ds_gnorm1_apply_images(_p(out), _p(x), _p(stats), _p(w), _p(b), f1, f2, stride, B, C, Ho, Wo, int(kind),
                                            1 if pool else 0, _stream()), "ds_gnorm1_apply_images")
     return out
@@ -1544,60 +1487,31 @@ def attention(qkv, E, out=None, precision="fp32", workspace=None, in_amax=None, 
     if E3 != 3 * E:
         raise ValueError("qkv must be [B, 3E, L]")
     heads = _check_heads(E, heads)
-    if heads > 1:
-        return _attention_heads(qkv, E, heads, out, precision, workspace, in_amax, out_amax)
-    if out is None:
-        out = torch.empty((B, E, L), dtype=torch.float32, device=qkv.device)
-    h3 = precision == "fp16x3" and L % 32 == 0 and E in (32, 64, 128, 256)
-    if h3:
-        if in_amax is None:
-            in_amax = amax_new(2 * B, qkv.device)
-            absmax_rows(qkv[:, :2 * E], out=in_amax[:B])
-            absmax_rows(qkv[:, 2 * E:], out=in_amax[B:])
-        pin, pout = (None if in_amax is NORMALISED else _pi(in_amax, 2 * B, "in_amax")), _pi(out_amax, B, "out_amax")
-    if h3 and _attention_uses_images(E, L, precision):
-        need = attention_workspace_floats(B, E, L)
-        if workspace is None:
-            workspace = torch.empty(need, dtype=torch.float32, device=qkv.device)
-        elif workspace.numel() < need:
-            raise ValueError("attention workspace too small")
-        N.check(N.lib().ds_attention_h3_ws(_p(out), _p(qkv), _p(workspace, "workspace"), B, E, L, pin, pout, _stream()),
-                "ds_attention_h3_ws")
-    elif h3:
-        N.check(N.lib().ds_attention_h3(_p(out), _p(qkv), B, E, L, pin, pout, _stream()), "ds_attention_h3")
-    else:
-        if L % 32 != 0 or E not in (32, 64, 128, 256, 384, 512):
-            N.check(N.lib().ds_attention_generic(_p(out), _p(qkv), B, E, L, _stream()), "ds_attention_generic")
+    out = _out(out, (B, E, L), qkv)
+    lib, d = N.lib(), E // heads
+    if not (precision == "fp16x3" and L % 32 == 0 and d in (32, 64, 128, 256)):
+        if heads > 1:
+            N.check(lib.ds_attention_heads_generic(_p(out), _p(qkv), B, E, heads, L, _stream()), "ds_attention_heads_generic")
+        elif L % 32 != 0 or E not in (32, 64, 128, 256, 384, 512):
+            N.check(lib.ds_attention_generic(_p(out), _p(qkv), B, E, L, _stream()), "ds_attention_generic")
         else:
-            N.check(N.lib().ds_attention(_p(out), _p(qkv), B, E, L, _stream()), "ds_attention")
+            N.check(lib.ds_attention(_p(out), _p(qkv), B, E, L, _stream()), "ds_attention")
         if out_amax is not None:
             absmax_rows(out, B, out=out_amax)
-    return out
-
-
-def _attention_heads(qkv, E, heads, out, precision, workspace, in_amax, out_amax):
-    B, _, L = qkv.shape
-    if out is None:
-        out = torch.empty((B, E, L), dtype=torch.float32, device=qkv.device)
-    d = E // heads
-    if precision == "fp16x3" and L % 32 == 0 and d in (32, 64, 128, 256):
-        if in_amax is None:          # one exponent pair per sample serves all its heads
-            in_amax = amax_new(2 * B, qkv.device)
-            absmax_rows(qkv[:, :2 * E], out=in_amax[:B])
-            absmax_rows(qkv[:, 2 * E:], out=in_amax[B:])
-        pin, pout = (None if in_amax is NORMALISED else _pi(in_amax, 2 * B, "in_amax")), _pi(out_amax, B, "out_amax")
-        need = attention_workspace_floats(B, E, L, precision, heads)
-        if need and workspace is None:
-            workspace = torch.empty(need, dtype=torch.float32, device=qkv.device)
-        elif need and workspace.numel() < need:
-            raise ValueError("attention workspace too small")
-        pws = _p(workspace, "workspace") if need else None
-        N.check(N.lib().ds_attention_h3_heads(_p(out), _p(qkv), pws, B, E, heads, L, pin, pout, _stream()),
-                "ds_attention_h3_heads")
+        return out
+    if in_amax is None:          # one exponent pair per sample serves all its heads
+        in_amax = amax_new(2 * B, qkv.device)
+        absmax_rows(qkv[:, :2 * E], out=in_amax[:B])
+        absmax_rows(qkv[:, 2 * E:], out=in_amax[B:])
+    pin, pout = (None if in_amax is NORMALISED else _pi(in_amax, 2 * B, "in_amax")), _pi(out_amax, B, "out_amax")
+    need = attention_workspace_floats(B, E, L, precision, heads)      # the image form by the head width (0: staged per workgroup)
+    pws = _p(_workspace(workspace, 4 * need, qkv, "attention workspace too small"), "workspace") if need else None
+    if heads > 1:
+        N.check(lib.ds_attention_h3_heads(_p(out), _p(qkv), pws, B, E, heads, L, pin, pout, _stream()), "ds_attention_h3_heads")
+    elif need:
+        N.check(lib.ds_attention_h3_ws(_p(out), _p(qkv), pws, B, E, L, pin, pout, _stream()), "ds_attention_h3_ws")
     else:
-        N.check(N.lib().ds_attention_heads_generic(_p(out), _p(qkv), B, E, heads, L, _stream()), "ds_attention_heads_generic")
-        if out_amax is not None:
-            absmax_rows(out, B, out=out_amax)
+        N.check(lib.ds_attention_h3(_p(out), _p(qkv), B, E, L, pin, pout, _stream()), "ds_attention_h3")
     return out
 
 
@@ -1606,20 +1520,21 @@ def linear(x, w, b=None, act=0, out=None):
     Nn, K2 = w.shape
     if K != K2:
         raise ValueError("linear: inner dimensions differ")
-    if out is None:
-        out = torch.empty((M, Nn), dtype=torch.float32, device=x.device)
+    _entries(b, Nn, "linear: b must have N={} entries", Nn)
+    out = _out(out, (M, Nn), x)
     N.check(N.lib().ds_linear(_p(out), _p(x), _p(w), _p(b), M, K, Nn, act, _stream()), "ds_linear")
     return out
 
 
 def fourier_features(t, W, add=None, out=None):
     M, half = t.numel(), W.numel()
-    if out is None:
-        out = torch.empty((M, 2 * half), dtype=torch.float32, device=t.device)
     add_rows = 0
     if add is not None:
+        if add.dim() < 1 or add.shape[-1] != 2 * half:
+            raise ValueError(f"fourier_features: add must hold rows of {2 * half} entries; got {tuple(add.shape)}")
         add = add.reshape(-1, 2 * half)
         add_rows = add.shape[0]
+    out = _out(out, (M, 2 * half), t)
     N.check(N.lib().ds_fourier_features(_p(out), _p(t), _p(W), _p(add), add_rows, M, half, _stream()),
             "ds_fourier_features")
     return out
@@ -1652,13 +1567,11 @@ def token_layernorm(x, w, b, mod=None, shift_chunk=0, scale_chunk=1, row=None, e
     if x.dim() != 3:
         raise ValueError("token_layernorm: x must be [B, E, L]")
     B, E, L = x.shape
-    for t, what in ((w, "weight"), (b, "bias")):
-        if t is not None and t.numel() != E:
-            raise ValueError(f"token_layernorm: {what} must have E={E} entries")
-    if out is None:
-        out = torch.empty_like(x)
-    elif tuple(out.shape) != (B, E, L) or out.data_ptr() == x.data_ptr():
+    _entries(w, E, "token_layernorm: weight must have E={} entries", E)
+    _entries(b, E, "token_layernorm: bias must have E={} entries", E)
+    if out is not None and out.data_ptr() == x.data_ptr():
         raise ValueError("token_layernorm: out must be a [B, E, L] tensor other than x")
+    out = _out(out, (B, E, L), x, "token_layernorm: out must be a [B, E, L] tensor other than x")
     psc = psh = None
     stride = 0
     if mod is not None:
@@ -1682,10 +1595,9 @@ def token_gate(x, y, mod, chunk=0, row=None, out=None):
     first, stride = _mod_rows(mod, E, B, row, "mod")
     if not 0 <= chunk < mod.shape[1] // E:
         raise ValueError("token_gate: chunk outside the table")
-    if out is None:
-        out = torch.empty_like(x)
-    elif tuple(out.shape) != (B, E, L) or out.data_ptr() == y.data_ptr():
+    if out is not None and out.data_ptr() == y.data_ptr():
         raise ValueError("token_gate: out must be [B, E, L] and may alias x only")
+    out = _out(out, (B, E, L), x, "token_gate: out must be [B, E, L] and may alias x only")
     N.check(N.lib().ds_token_gate(_p(out, "out"), _p(x, "x"), _p(y, "y"), mod.data_ptr() + 4 * (first + chunk * E), stride, B, E, L,
                                   _stream()), "ds_token_gate")
     return out
@@ -1695,10 +1607,7 @@ def silu_amax(x, out=None, out_amax=None):
     """SiLU(x) for x [B, ...] (out may be x), the per-sample max |out| merged into out_amax (int32 [B]) when given."""
     require_device(x, "x")
     B = x.shape[0]
-    if out is None:
-        out = torch.empty_like(x)
-    elif tuple(out.shape) != tuple(x.shape):
-        raise ValueError("silu_amax: out must have x's shape")
+    out = _out(out, x.shape, x, "silu_amax: out must have x's shape")
     N.check(N.lib().ds_silu_amax(_p(out, "out"), _p(x, "x"), B, x.numel() // max(B, 1), _pi(out_amax, B, "out_amax"), _stream()),
             "ds_silu_amax")
     return out
@@ -1721,10 +1630,7 @@ def patch_embed(x, w, bias, patch, out=None):
     E = w.shape[0]
     if tuple(w.shape) != (E, C * patch * patch) or (bias is not None and bias.numel() != E):
         raise ValueError(f"patch_embed: weight must be [E, {C * patch * patch}] and bias [E]; got {tuple(w.shape)}")
-    if out is None:
-        out = torch.empty((B, E, L), dtype=torch.float32, device=x.device)
-    elif tuple(out.shape) != (B, E, L):
-        raise ValueError(f"patch_embed: out must be {(B, E, L)}")
+    out = _out(out, (B, E, L), x, "patch_embed: out must be {1}")
     N.check(N.lib().ds_patch_embed(_p(out, "out"), _p(x, "x"), _p(w, "weight"), _p(bias, "bias"), B, C, H, W, patch, E, _stream()),
             "ds_patch_embed")
     return out
@@ -1740,10 +1646,7 @@ def patch_unembed(x, w, bias, patch, shape, out=None):
     K = C * patch * patch
     if tuple(w.shape) != (K, E) or (bias is not None and bias.numel() != K):
         raise ValueError(f"patch_unembed: weight must be [{K}, {E}] and bias [{K}]; got {tuple(w.shape)}")
-    if out is None:
-        out = torch.empty((B, C, H, W), dtype=torch.float32, device=x.device)
-    elif tuple(out.shape) != (B, C, H, W):
-        raise ValueError(f"patch_unembed: out must be {(B, C, H, W)}")
+    out = _out(out, (B, C, H, W), x, "patch_unembed: out must be {1}")
     N.check(N.lib().ds_patch_unembed(_p(out, "out"), _p(x, "x"), _p(w, "weight"), _p(bias, "bias"), B, C, H, W, patch, E, _stream()),
             "ds_patch_unembed")
     return out
@@ -1757,8 +1660,7 @@ def fourier_channels(x, W, out=None):
         raise ValueError(f"fourier_channels: W must be [{C}, D]; got {tuple(W.shape)}")
     D = W.shape[1]
     HW = x.numel() // max(B * C, 1)
-    if out is None:
-        out = torch.empty((B, 2 * D) + tuple(x.shape[2:]), dtype=torch.float32, device=x.device)
+    out = _out(out, (B, 2 * D) + tuple(x.shape[2:]), x)
     N.check(N.lib().ds_fourier_channels(_p(out, "out"), _p(x, "x"), _p(W, "W"), B, C, D, HW, _stream()), "ds_fourier_channels")
     return out
 

@@ -15,6 +15,7 @@ DS_IN_NETWORK, DS_IN_SCORE, DS_IN_DRIFT, DS_IN_FLOW = 0, 1, 2, 3
 DS_LOAD_PLAIN, DS_LOAD_MAXPOOL2, DS_LOAD_UPSAMPLE2, DS_LOAD_AVGPOOL2 = 0, 1, 2, 3
 DS_PAD_CIRCULAR = 16
 DS_RES1_UPSAMPLED = 32
+DS_PC_RAW, DS_PC_IMAGES = 1, 2
 
 
 class EvalCoef(Structure):
@@ -56,6 +57,9 @@ _PROTOS = {
     "ds_conv2d_h3_packed_bytes": (c_size_t, [c_int, c_int]),
     "ds_conv2d_h3_pack_weights": (c_int, [_P, _P, c_int, c_int, c_int, _P]),
     "ds_conv2d_h3": (c_int, [_P, _P, _P, c_int, _P, _P, c_int, _P, _P, c_int, c_int, c_int, c_int, c_int, c_int, _P, _P, _P, _P, _P]),
+    # (the stream is not the last argument: pooled is an answer written on the host, and the flags word closes the list)
+    "ds_conv2d_h3_pc": (c_int, [_P, _P, _P, c_int, _P, _P, c_int, _P, _P, c_int, c_int, c_int, c_int, c_int, c_int, _P, _P, _P, _P, _P,
+                                _P, POINTER(c_int), c_int]),
     "ds_absmax_rows": (c_int, [_P, _P, c_int, c_size_t, c_size_t, _P]),
     "ds_amax_merge": (c_int, [_P, _P, _P, c_int, _P]),
     "ds_absmax_channels": (c_int, [_P, _P, _P, _P, _P, c_int, c_int, c_size_t, c_int, _P]),

@@ -825,10 +825,12 @@ int ds_conv2d_h3_pack_weights(void* packed, const float* w, int Cout, int Cin, i
   return DS_OK;
 }
 
-int ds_conv2d_h3(float* out, const float* in, const void* w_packed, int wshift, const float* bias, const float* shift,
-                 int shift_stride, const float* res1, const float* res2, int B, int Cin, int Cout, int H, int W,
-                 int load_mode, const float* prenorm, float* tile_stats, const unsigned* in_amax, unsigned* out_amax,
-                 void* stream) {
+// ds_conv2d_h3 and ds_conv2d_h3_pc.  raw: a launch without prenorm may take the persistent kernel; pool_out / pooled: see
+// ds_conv3h_args.h (pooled == NULL: no pooled output asked for)
+static int conv2d_h3(float* out, const float* in, const void* w_packed, int wshift, const float* bias, const float* shift,
+                     int shift_stride, const float* res1, const float* res2, int B, int Cin, int Cout, int H, int W,
+                     int load_mode, const float* prenorm, float* tile_stats, const unsigned* in_amax, unsigned* out_amax,
+                     void* stream, bool raw, float* pool_out, bool* pooled) {
   DS_REQUIRE(out && in && w_packed, DS_ERR_NULL, "ds_conv2d_h3: NULL pointer");
   DS_REQUIRE(!(prenorm && in_amax), DS_ERR_UNSUPPORTED, "ds_conv2d_h3: in_amax is for raw inputs (with prenorm the table's fourth column carries the exponent)");
   DS_REQUIRE(B >= 0 && Cin > 0 && Cout > 0 && H > 0 && W > 0, DS_ERR_SHAPE,
@@ -867,6 +869,7 @@ int ds_conv2d_h3(float* out, const float* in, const void* w_packed, int wshift, 
   a.out = out; a.in = in; a.wp = reinterpret_cast<const u32x4*>(w_packed); a.bias = bias; a.shift = shift;
   a.res1 = res1; a.res2 = res2; a.shift_stride = shift_stride;
   a.wshift = wshift; a.in_amax = in_amax; a.out_amax = out_amax;
+  a.pool_out = pool_out;
   a.B = B; a.Cin = Cin; a.Cout = Cout; a.H = H; a.W = W;
   a.Hin = load_mode == DS_LOAD_MAXPOOL2 ? 2 * H : (load_mode == DS_LOAD_UPSAMPLE2 ? H / 2 : H);
   a.Win = load_mode == DS_LOAD_MAXPOOL2 ? 2 * W : (load_mode == DS_LOAD_UPSAMPLE2 ? W / 2 : W);
@@ -887,7 +890,7 @@ int ds_conv2d_h3(float* out, const float* in, const void* w_packed, int wshift, 
   if (!w16 && load_mode == DS_LOAD_PLAIN && conv3h_shape16()) {
     // the persistent producer / consumer form (ds_conv3p.hip) takes the launches whose shape is its own
     bool launched = false;
-    const int rc = conv3p_try_launch(a, s, &launched);
+    const int rc = conv3p_try_launch(a, s, &launched, raw, pooled);
     if (rc != DS_OK || launched) return rc;
   }
 #define DS_L3(M, W) (prenorm ? launch_conv3h<M, W, true>(a, s) : launch_conv3h<M, W, false>(a, s))
@@ -907,9 +910,9 @@ size_t ds_conv_images_bytes(int B, int C, int H, int W) {
   return (size_t)B * ((C + KC - 1) / KC) * 4 * (size_t)(H + 2) * (W + 2) * 16;
 }
 
-int ds_conv2d_h3_img(float* out, const void* images, const void* w_packed, int wshift, const float* bias, const float* shift,
-                     int shift_stride, const float* res1, const float* res2, int B, int Cin, int Cout, int H, int W,
-                     int flags, float* tile_stats, unsigned* out_amax, void* stream) {
+static int conv2d_h3_img(float* out, const void* images, const void* w_packed, int wshift, const float* bias, const float* shift,
+                         int shift_stride, const float* res1, const float* res2, int B, int Cin, int Cout, int H, int W,
+                         int flags, float* tile_stats, unsigned* out_amax, void* stream, float* pool_out, bool* pooled) {
   DS_REQUIRE(out && images && w_packed, DS_ERR_NULL, "ds_conv2d_h3_img: NULL pointer");
   DS_REQUIRE((flags & ~DS_RES1_UPSAMPLED) == 0, DS_ERR_UNSUPPORTED, "ds_conv2d_h3_img: flags %d (DS_RES1_UPSAMPLED only)", flags);
   DS_REQUIRE(!(flags & DS_RES1_UPSAMPLED) || (res1 && H % 2 == 0 && W % 2 == 0 && (reinterpret_cast<uintptr_t>(res1) & 7u) == 0),
@@ -931,6 +934,7 @@ int ds_conv2d_h3_img(float* out, const void* images, const void* w_packed, int w
   a.bias = bias; a.shift = shift; a.res1 = res1; a.res2 = res2; a.shift_stride = shift_stride; a.tile_stats = tile_stats;
   a.res1_up = (flags & DS_RES1_UPSAMPLED) ? 1 : 0;
   a.wshift = wshift; a.out_amax = out_amax;
+  a.pool_out = pool_out;
   a.B = B; a.Cin = Cin; a.Cout = Cout; a.H = H; a.W = W; a.Hin = H; a.Win = W;
   const long long pad32 = (long long)((W + 31) / 32 * 32) * ((H + 7) / 8 * 8);
   const long long pad16 = (long long)((W + 15) / 16 * 16) * ((H + 15) / 16 * 16);
@@ -946,11 +950,49 @@ int ds_conv2d_h3_img(float* out, const void* images, const void* w_packed, int w
   hipStream_t s = ds::as_stream(stream);
   if (!w16) {
     bool launched = false;
-    const int rc = conv3p_try_launch_img(a, s, &launched);
+    const int rc = conv3p_try_launch_img(a, s, &launched, pooled);
     if (rc != DS_OK || launched) return rc;
   }
   return w16 ? launch_conv3h_w<DS_LOAD_PLAIN, true, false, false, 4, true, true>(a, s)
              : launch_conv3h_w<DS_LOAD_PLAIN, false, false, false, 4, true, true>(a, s);
+}
+
+int ds_conv2d_h3(float* out, const float* in, const void* w_packed, int wshift, const float* bias, const float* shift,
+                 int shift_stride, const float* res1, const float* res2, int B, int Cin, int Cout, int H, int W,
+                 int load_mode, const float* prenorm, float* tile_stats, const unsigned* in_amax, unsigned* out_amax,
+                 void* stream) {
+  return conv2d_h3(out, in, w_packed, wshift, bias, shift, shift_stride, res1, res2, B, Cin, Cout, H, W, load_mode, prenorm, tile_stats,
+                   in_amax, out_amax, stream, false, nullptr, nullptr);
+}
+
+int ds_conv2d_h3_img(float* out, const void* images, const void* w_packed, int wshift, const float* bias, const float* shift,
+                     int shift_stride, const float* res1, const float* res2, int B, int Cin, int Cout, int H, int W,
+                     int flags, float* tile_stats, unsigned* out_amax, void* stream) {
+  return conv2d_h3_img(out, images, w_packed, wshift, bias, shift, shift_stride, res1, res2, B, Cin, Cout, H, W, flags, tile_stats,
+                       out_amax, stream, nullptr, nullptr);
+}
+
+int ds_conv2d_h3_pc(float* out, const float* in, const void* w_packed, int wshift, const float* bias, const float* shift,
+                    int shift_stride, const float* res1, const float* res2, int B, int Cin, int Cout, int H, int W,
+                    int load_mode, const float* prenorm, float* tile_stats, const unsigned* in_amax, unsigned* out_amax,
+                    void* stream, float* pool_out, int* pooled, int flags) {
+  DS_REQUIRE((flags & ~(DS_PC_RAW | DS_PC_IMAGES)) == 0, DS_ERR_UNSUPPORTED, "ds_conv2d_h3_pc: flags %d", flags);
+  DS_REQUIRE(!pool_out || pooled, DS_ERR_NULL, "ds_conv2d_h3_pc: pool_out without a place for the answer (pooled)");
+  DS_REQUIRE((reinterpret_cast<uintptr_t>(pool_out) & 7u) == 0, DS_ERR_SHAPE, "ds_conv2d_h3_pc: pool_out must be 8-byte aligned");
+  DS_REQUIRE(!pool_out || (H % 2 == 0 && W % 2 == 0), DS_ERR_SHAPE, "ds_conv2d_h3_pc: pool_out needs even H, W (got %d x %d)", H, W);
+  if (pooled) *pooled = 0;
+  bool did = false;
+  int rc;
+  if (flags & DS_PC_IMAGES) {
+    DS_REQUIRE(!prenorm && !in_amax, DS_ERR_UNSUPPORTED, "ds_conv2d_h3_pc: image input carries its own activation (no prenorm, no in_amax)");
+    rc = conv2d_h3_img(out, in, w_packed, wshift, bias, shift, shift_stride, res1, res2, B, Cin, Cout, H, W, load_mode, tile_stats,
+                       out_amax, stream, pool_out, pool_out ? &did : nullptr);
+  } else {
+    rc = conv2d_h3(out, in, w_packed, wshift, bias, shift, shift_stride, res1, res2, B, Cin, Cout, H, W, load_mode, prenorm, tile_stats,
+                   in_amax, out_amax, stream, (flags & DS_PC_RAW) != 0, pool_out, pool_out ? &did : nullptr);
+  }
+  if (rc == DS_OK && pooled) *pooled = did ? 1 : 0;
+  return rc;
 }
 
 }  // extern "C"

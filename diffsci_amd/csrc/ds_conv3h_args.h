@@ -70,6 +70,7 @@ struct Conv3hArgs {
   int pc_prio;              // ds_conv3p.hip only: s_setprio level of the producer waves (DS_CONV_PC_PRIO, A/B runs)
   int pc_skew_mask;         // ds_conv3p.hip only: mask of the start-up stagger (DS_CONV_PC_SKEW)
   int two_early;            // ds_conv3h.hip, two channel tiles per workgroup: waves 0-3 stage the next patch before the step's matrix instructions (DS_CONV_TWO_EARLY)
+  float* pool_out;          // ds_conv3p.hip only: [B, Cout, H/2, W/2] receives MaxPool2d(2) of the stored values, or NULL (the last member: every other offset stays)
 #ifdef DS_STAMP
   unsigned long long* stamps;   // diagnostic build only (tools/conv3h_stamp.hip)
 #endif
@@ -79,8 +80,10 @@ struct Conv3hArgs {
 // ds_conv3p.hip: the persistent producer / consumer form of the fused-loader launches (full tiles, an even number of 16-channel
 // chunks, enough tiles to give every CU several).  Returns DS_OK and sets *launched when it took the launch; leaves *launched
 // false (and launches nothing) when the shape is not its own.
-int conv3p_try_launch(const Conv3hArgs& a, hipStream_t s, bool* launched);
+// raw: a launch without prenorm may take it too (otherwise only under DS_CONV_PC=3).  pooled (may be NULL: a.pool_out is ignored): set
+// when the launch also wrote a.pool_out -- a fused-loader or image-input launch with a residual and zero padding.
+int conv3p_try_launch(const Conv3hArgs& a, hipStream_t s, bool* launched, bool raw = false, bool* pooled = nullptr);
 // ... the image-input form (ds_conv2d_h3_img; full 8 x 32 tiles, Cin and Cout multiples of 64, no half-resolution residual)
-int conv3p_try_launch_img(const Conv3hArgs& a, hipStream_t s, bool* launched);
+int conv3p_try_launch_img(const Conv3hArgs& a, hipStream_t s, bool* launched, bool* pooled = nullptr);
 
 }  // namespace ds_conv3

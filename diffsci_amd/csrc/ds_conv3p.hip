@@ -30,6 +30,10 @@
 //     item's first two chunk pairs;
 //   * IMG: pre-split image input (the 256-channel level) -- the producers issue DMA only (image patches in front of the weight slab).
 //
+//   * POOL (after the round): the store phase of a residual block's second convolution also writes MaxPool2d(2) of what it stores --
+//     the DownSampler's input, a quarter of the size, two 8-byte store instructions per batch of four -- and the DownSampler is then a
+//     plain raw-input launch of this kernel (ds_conv2d_h3_pc; DESIGN.md 4.5, profiles/pool_route.log).
+//
 // Shapes it takes (the launcher falls back to ds_conv3h.hip otherwise): plain load, 8 x 32 pixel tiles that tile the plane
 // exactly, Cout and Cin multiples of 64, and enough items to give every CU several.
 #include "ds_conv3h_args.h"
@@ -123,9 +127,13 @@ __device__ __forceinline__ unsigned const_u32(const void* p, size_t i) {
 // IMG: the input arrives as pre-split fp16 hi / lo images (ds_inorm_silu_images; ds_conv3h.hip, IMGIN) -- the 256-channel level of
 // config 2.  The producers then only issue DMA: an X buffer is filled by 22 wave-instructions (the one-shot kernel's plan, lane for
 // lane), the weight slabs stay with them too (only the staging forms hand them to the consumers), and the consumers are pure matrix streams.
-template <bool PRE, bool CIRC, int NRES, bool VEC = false, bool IMG = false>
+// POOL: the store phase also writes MaxPool2d(2) of the stored values to a.pool_out [B, Cout, H/2, W/2] (the DownSampler's input, so
+// that its loader need not read four raw pixels per element once per channel tile).  A template parameter for NRES's reason: the
+// launches that do not pool keep their instruction stream.  Only the forms the last block of a level can be (static_assert).
+template <bool PRE, bool CIRC, int NRES, bool VEC = false, bool IMG = false, bool POOL = false>
 __global__ __launch_bounds__(512, 2) void k_conv3p(const Conv3hArgs a) {
   static_assert(!IMG || (!PRE && !CIRC && !VEC), "image input: plain zero-padded form");
+  static_assert(!POOL || ((PRE || IMG) && !CIRC && NRES >= 1), "pooled output: a residual block's second convolution, zero padding");
   constexpr int PW = Geo<false>::PW, NPOS = Geo<false>::NPOS;
   constexpr int HS = NPOS + HPAD16, PS = 2 * NPOS + HPAD16, XBV = XBUF_VEC16;
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -570,6 +578,7 @@ __global__ __launch_bounds__(512, 2) void k_conv3p(const Conv3hArgs a) {
   // head of its own tile, behind the batch that has just read it.
   int s_b = 0, s_cot = 0, s_tile = 0;
   size_t s_idx = 0;                                  // the lane's first output element
+  size_t s_pidx = 0;                                 // POOL: the lane's first pooled element
   const size_t s_step = 4 * (size_t)HW;
   float s_amax = 0.f;
   const int p4 = 4 * (lane & 7);
@@ -581,6 +590,11 @@ __global__ __launch_bounds__(512, 2) void k_conv3p(const Conv3hArgs a) {
     const size_t ch = (size_t)it.b * a.Cout + it.cot * COT + (lane >> 4);
     s_idx = ch * HW + (size_t)gy * a.W + gx;
     s_amax = 0.f;
+    // lanes l and l ^ 8 of a store instruction hold the same four columns of the tile's two rows of one channel: the 2 x 2 maxima of
+    // store instructions k and k + 1 (four channels each) make ONE 64-lane 8-byte store, the upper row's lanes storing k's two
+    // pooled pixels and the lower row's lanes k + 1's.  Pooled row (y0 + 2 rw) / 2, columns (x0 + p4) / 2 and the next.
+    if constexpr (POOL)
+      s_pidx = ((ch + 4 * ((lane >> 3) & 1)) * (size_t)(a.H >> 1) + (size_t)((it.y0 >> 1) + rw)) * (size_t)(a.W >> 1) + (size_t)((gx) >> 1);
   };
   // residual vectors of one batch.  (No half-resolution res1 here: with both forms in one function the two loads share destination
   // registers, and hipcc then waits for vmcnt(0) in front of every residual load -- the launcher keeps such launches on ds_conv3h.hip.)
@@ -611,6 +625,25 @@ __global__ __launch_bounds__(512, 2) void k_conv3p(const Conv3hArgs a) {
     }
 #pragma unroll
     for (int k = 0; k < BK; ++k) *reinterpret_cast<f32x4*>(a.out + s_idx + (size_t)(half * BK + k) * s_step) = v[k];
+    if constexpr (POOL) {
+      // horizontal pair maxima in the lane, the vertical maximum with the lane 8 away (row_ror:8, no LDS), in the max-pool loader's
+      // order of operations (ds_conv3h.hip)
+      const bool low = (lane >> 3) & 1;
+      float mx[BK], my[BK];
+#pragma unroll
+      for (int k = 0; k < BK; ++k) {
+        const float hx = fmaxf(v[k].x, v[k].y), hy = fmaxf(v[k].z, v[k].w);
+        const float ox = __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, hx), 0x128, 0xF, 0xF, true));
+        const float oy = __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, hy), 0x128, 0xF, 0xF, true));
+        mx[k] = low ? fmaxf(ox, hx) : fmaxf(hx, ox);         // (upper row's pair, lower row's pair) in both lanes
+        my[k] = low ? fmaxf(oy, hy) : fmaxf(hy, oy);
+      }
+#pragma unroll
+      for (int k = 0; k < BK; k += 2) {
+        const float2 pv = low ? float2{mx[k + 1], my[k + 1]} : float2{mx[k], my[k]};
+        *reinterpret_cast<float2*>(a.pool_out + s_pidx + (size_t)(half * BK + k) * (size_t)HW) = pv;     // 4 channels x HW / 4 per store instruction
+      }
+    }
     if (want_amax) {
 #pragma unroll
       for (int k = 0; k < BK; ++k) s_amax = fmaxf(s_amax, ds_epi::abs_max4(v[k]));
@@ -632,7 +665,7 @@ __global__ __launch_bounds__(512, 2) void k_conv3p(const Conv3hArgs a) {
         for (int k = 0; k < BK; ++k) *reinterpret_cast<f32x4*>(&tile[4 * (4 * (half * BK + k) + (lane >> 4))]) = o[k];
       }
     }
-    return BK;
+    return POOL ? BK + BK / 2 : BK;
   };
   auto commit_amax_asm = [&]() __attribute__((always_inline)) {        // ds_epi::commit_amax with the atomic as assembly
     float m = s_amax;
@@ -938,11 +971,11 @@ __global__ __launch_bounds__(512, 2) void k_conv3p(const Conv3hArgs a) {
   }
 }
 
-template <bool PRE, bool CIRC, int NRES, bool VEC = false, bool IMG = false>
+template <bool PRE, bool CIRC, int NRES, bool VEC = false, bool IMG = false, bool POOL = false>
 int launch_conv3p_w(const Conv3hArgs& a, int wgs, hipStream_t s) {
-  const int rc = ds::ensure_dynamic_lds<&k_conv3p<PRE, CIRC, NRES, VEC, IMG>>(P_LDS, "hipFuncSetAttribute(conv3p)");
+  const int rc = ds::ensure_dynamic_lds<&k_conv3p<PRE, CIRC, NRES, VEC, IMG, POOL>>(P_LDS, "hipFuncSetAttribute(conv3p)");
   if (rc != DS_OK) return rc;
-  hipLaunchKernelGGL((k_conv3p<PRE, CIRC, NRES, VEC, IMG>), dim3((unsigned)wgs), dim3(512), P_LDS, s, a);
+  hipLaunchKernelGGL((k_conv3p<PRE, CIRC, NRES, VEC, IMG, POOL>), dim3((unsigned)wgs), dim3(512), P_LDS, s, a);
   DS_CHECK_LAUNCH("ds_conv2d_h3 (persistent)");
   return DS_OK;
 }
@@ -951,11 +984,15 @@ bool conv3p_vec() {
   static const bool on = [] { const char* e = getenv("DS_CONV_VEC"); return !(e && atoi(e) == 0); }();
   return on;
 }
-template <bool PRE, bool CIRC, int NRES>
+template <bool PRE, bool CIRC, int NRES, bool POOL = false>
 int launch_conv3p_r(const Conv3hArgs& a, int wgs, hipStream_t s) {
   // 16-byte patch loads: W is a multiple of 32 and Cin of 64 here (conv3p_try_launch); no column tap offset, an aligned input
-  if (conv3p_vec() && a.ox == 0 && (reinterpret_cast<uintptr_t>(a.in) & 15u) == 0) return launch_conv3p_w<PRE, CIRC, NRES, true>(a, wgs, s);
-  return launch_conv3p_w<PRE, CIRC, NRES>(a, wgs, s);
+  if (conv3p_vec() && a.ox == 0 && (reinterpret_cast<uintptr_t>(a.in) & 15u) == 0) return launch_conv3p_w<PRE, CIRC, NRES, true, false, POOL>(a, wgs, s);
+  return launch_conv3p_w<PRE, CIRC, NRES, false, false, POOL>(a, wgs, s);
+}
+// pooled output: a residual block's second convolution (at least one residual), zero padding, fused-loader or image input
+bool conv3p_pool_ok(const Conv3hArgs& a, bool img) {
+  return a.pool_out && (img || a.prenorm) && !a.circular && (a.res1 || a.res2) && (reinterpret_cast<uintptr_t>(a.pool_out) & 7u) == 0;
 }
 void conv3p_fill_args(Conv3hArgs& a) {
   a.ntiles_magic40 = (1ull << 40) / (unsigned long long)(a.tiles_x * a.tiles_y) + 1ull;
@@ -972,6 +1009,9 @@ void conv3p_fill_args(Conv3hArgs& a) {
 template <bool PRE, bool CIRC>
 int launch_conv3p(Conv3hArgs a, int wgs, hipStream_t s) {
   conv3p_fill_args(a);
+  if constexpr (PRE && !CIRC) {
+    if (a.pool_out) return a.res2 ? launch_conv3p_r<PRE, CIRC, 2, true>(a, wgs, s) : launch_conv3p_r<PRE, CIRC, 1, true>(a, wgs, s);
+  }
   if (!a.res1) return launch_conv3p_r<PRE, CIRC, 0>(a, wgs, s);
   return a.res2 ? launch_conv3p_r<PRE, CIRC, 2>(a, wgs, s) : launch_conv3p_r<PRE, CIRC, 1>(a, wgs, s);
 }
@@ -1007,8 +1047,9 @@ int conv3p_cus() {
 }  // namespace
 
 // Image input (ds_conv2d_h3_img): DS_CONV_PC_IMG=0 keeps the one-shot kernel (A/B runs).
-int conv3p_try_launch_img(const Conv3hArgs& a0, hipStream_t s, bool* launched) {
+int conv3p_try_launch_img(const Conv3hArgs& a0, hipStream_t s, bool* launched, bool* pooled) {
   *launched = false;
+  if (pooled) *pooled = false;
   static const bool on = [] { const char* e = getenv("DS_CONV_PC_IMG"); return !(e && atoi(e) == 0); }();
   if (!on || conv3p_mode() == 0) return DS_OK;
   if (a0.H % 8 != 0 || a0.W % 32 != 0 || a0.Cout % COT != 0 || a0.Cin % (4 * KC) != 0 || a0.res1_up) return DS_OK;
@@ -1018,15 +1059,22 @@ int conv3p_try_launch_img(const Conv3hArgs& a0, hipStream_t s, bool* launched) {
   if ((long long)4 * (a0.H + 2) * (a0.W + 2) * 16 >= (1ll << 31)) return DS_OK;       // the DMA's 32-bit lane offsets stay inside one (sample, chunk)
   Conv3hArgs a = a0;
   conv3p_fill_args(a);
+  const bool pool = pooled && conv3p_pool_ok(a, true);
+  if (!pool) a.pool_out = nullptr;
   int rc;
-  if (!a.res1) rc = launch_conv3p_w<false, false, 0, false, true>(a, wgs, s);
+  if (pool) rc = a.res2 ? launch_conv3p_w<false, false, 2, false, true, true>(a, wgs, s) : launch_conv3p_w<false, false, 1, false, true, true>(a, wgs, s);
+  else if (!a.res1) rc = launch_conv3p_w<false, false, 0, false, true>(a, wgs, s);
   else rc = a.res2 ? launch_conv3p_w<false, false, 2, false, true>(a, wgs, s) : launch_conv3p_w<false, false, 1, false, true>(a, wgs, s);
-  if (rc == DS_OK) *launched = true;
+  if (rc == DS_OK) { *launched = true; if (pooled) *pooled = pool; }
   return rc;
 }
 
-int conv3p_try_launch(const Conv3hArgs& a, hipStream_t s, bool* launched) {
+int conv3p_try_launch(const Conv3hArgs& a0, hipStream_t s, bool* launched, bool raw, bool* pooled) {
   *launched = false;
+  if (pooled) *pooled = false;
+  Conv3hArgs a = a0;
+  const bool pool = pooled && conv3p_pool_ok(a, false);
+  if (!pool) a.pool_out = nullptr;
   const int mode = conv3p_mode();
   if (mode == 0) return DS_OK;
   if (a.H % 8 != 0 || a.W % 32 != 0 || a.Cout % COT != 0 || a.Cin % (4 * KC) != 0) return DS_OK;      // an even number of chunk PAIRS (the consumer's two fragment sets)
@@ -1035,11 +1083,11 @@ int conv3p_try_launch(const Conv3hArgs& a, hipStream_t s, bool* launched) {
   const int wgs = conv3p_cus() / 8 * 8;               // a multiple of the XCD count: the item order assumes round-robin dealing
   if (wgs <= 0 || total < (long long)wgs * conv3p_min_items() || total >= (1ll << 22)) return DS_OK;      // 2^22: the exactness bound of the item decode
   if (a.n_cot % 2 == 0 && a.prenorm && mode < 2) return DS_OK;     // the two-channel-tile kernel's launches
-  if (!a.prenorm && mode < 3) return DS_OK;           // raw-input launches: measured separately (DS_CONV_PC=3)
+  if (!a.prenorm && mode < 3 && !raw) return DS_OK;   // raw-input launches: where the caller asks (ds_conv2d_h3_pc, DS_PC_RAW), or all of them (DS_CONV_PC=3)
   int rc;
   if (a.prenorm) rc = a.circular ? launch_conv3p<true, true>(a, wgs, s) : launch_conv3p<true, false>(a, wgs, s);
   else rc = a.circular ? launch_conv3p<false, true>(a, wgs, s) : launch_conv3p<false, false>(a, wgs, s);
-  if (rc == DS_OK) *launched = true;
+  if (rc == DS_OK) { *launched = true; if (pooled) *pooled = pool; }
   return rc;
 }
 

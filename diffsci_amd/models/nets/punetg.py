@@ -28,6 +28,9 @@ from . import precision, runtime
 from .punetg_config import PUNetGConfig, scale_factor
 from .runtime import AmaxArena, Workspace, require_eval, shift_rows, weights_signature
 
+POOL_ROUTES = ("loader", "pass", "epilogue")
+POOL_ROUTE_DEFAULT = "epilogue"
+
 
 class _AffineHolder(torch.nn.Module):
     """weight/bias container for GroupRMSNorm / GroupPixNorm (commonlayers.py:332-361, 387-414); no parameters
@@ -334,6 +337,13 @@ class PUNetG(torch.nn.Module):
         # tiles every tile's workgroup would redo the activation of the same input patch (5.3x the transcendental
         # work of a standalone pass at Cout = 256), and the standalone kernel wins
         self.fuse_max_cot = 2
+        # The DownSampler's MaxPool2d(2) (fields, fp16x3, 3x3 transition kernel; every route gives the same bits):
+        #   "loader"  : the convolution's loader pools (DS_LOAD_MAXPOOL2: four raw pixels per element, once per channel tile)
+        #   "pass"    : a pooling pass (ops.maxpool_f), then a plain convolution on the persistent kernel
+        #   "epilogue": the level's last residual block writes the pooled tensor from its store phase (ops.PoolOut) and the plain
+        #               convolution follows; where that launch does not qualify, the loader
+        # DIFFSCI_POOL_ROUTE sets the default (A/B runs)
+        self.pool_route = os.environ.get("DIFFSCI_POOL_ROUTE", POOL_ROUTE_DEFAULT)
         # Standalone norms hand their convolutions pre-split fp16 images (ops.inorm_silu_images / ops.conv_img) where the layer
         # qualifies (_norm_images_ok); DIFFSCI_NORM_IMAGES=0 keeps the fp32 route (A/B runs)
         self.norm_images = os.environ.get("DIFFSCI_NORM_IMAGES", "1") != "0"
@@ -803,10 +813,11 @@ class PUNetG(torch.nn.Module):
             return None
         return ws.take((B, C, ops.conv_tile_count(H, W), 4), dev)
 
-    def _res(self, blk, x, shift, pk, ws, res2=None, xs=None, want_stats=True, out_amax=None):
+    def _res(self, blk, x, shift, pk, ws, res2=None, xs=None, want_stats=True, out_amax=None, pool=None):
         """ResnetBlockC.forward (commonlayers.py:824-833); returns (fresh buffer, its tile statistics);
         x untouched.  xs = tile statistics of x (from the convolution that produced it) or None.  out_amax: a zeroed amax row
-        that receives the per-sample max |result| (the result feeds a raw-input launch: Down/UpSampler, attention)."""
+        that receives the per-sample max |result| (the result feeds a raw-input launch: Down/UpSampler, attention).  pool: an
+        ops.PoolOut that conv2's store phase may fill with MaxPool2d(2) of the result (pool.written tells)."""
         B, C, H, W = x.shape
         dev = x.device
         if self.extra_residual is not None:
@@ -827,15 +838,15 @@ class PUNetG(torch.nn.Module):
             return y, None                                          # no tile statistics of the sum: the consumer normalises standalone
         if isinstance(shift, _FieldShifts):                # a field of time shifts: conv1's epilogue adds it as a residual
             yt = self._field_shift(blk, shift, H, W)
-            got = self._res_body(blk, x, None, yt, pk, ws, res2, xs, want_stats, out_amax)
+            got = self._res_body(blk, x, None, yt, pk, ws, res2, xs, want_stats, out_amax, pool)
             ws.give(yt)
             return got
         yt = None
         if shift is not None and shift.dim() == 4:         # the same, handed over as a tensor [B, C, He, We]
             yt, shift = self._rescale_shift_field(shift, H, W), None
-        return self._res_body(blk, x, shift, yt, pk, ws, res2, xs, want_stats, out_amax)
+        return self._res_body(blk, x, shift, yt, pk, ws, res2, xs, want_stats, out_amax, pool)
 
-    def _res_body(self, blk, x, shift, yt, pk, ws, res2, xs, want_stats, out_amax):
+    def _res_body(self, blk, x, shift, yt, pk, ws, res2, xs, want_stats, out_amax, pool=None):
         B, C, H, W = x.shape
         dev = x.device
         k1, k2 = self.norm_kinds                           # 0 GroupLN, 1 GroupRMS, 2 none, 3 GroupPix (not a table)
@@ -854,7 +865,7 @@ class PUNetG(torch.nn.Module):
             ops.inorm_table(ys, w2, b2, k2, H * W, eps=1e-5, out=tab)
             os_ = self._stats_buf(ws, B, C, H, W, dev) if want_stats else None
             out = self._conv(blk.conv2, y, pk, res1=x, res2=res2, prenorm=tab, tile_stats=os_, out=ws.take(x.shape, dev),
-                             out_amax=out_amax)
+                             out_amax=out_amax, **({} if pool is None else {"pool": pool}))
             ws.give(y)
             ws.give(ys)
             ws.give(tab)
@@ -868,7 +879,7 @@ class PUNetG(torch.nn.Module):
             ops.inorm_silu_images(y, w2, b2, k2, eps=1e-5, out=img)
             os_ = self._stats_buf(ws, B, C, H, W, dev) if want_stats else None
             out = ops.conv_img(img, pk[id(blk.conv2)], B, C, H, W, bias=blk.conv2.bias, res1=x, res2=res2, tile_stats=os_,
-                               out=ws.take(x.shape, dev), out_amax=out_amax)
+                               out=ws.take(x.shape, dev), out_amax=out_amax, pool=pool)
             ws.give(img)
             ws.give(y)
             return out, os_
@@ -885,7 +896,7 @@ class PUNetG(torch.nn.Module):
             ops.table_apply_images(y, tab, out=img)
             os_ = self._stats_buf(ws, B, C, H, W, dev) if want_stats else None
             out = ops.conv_img(img, pk[id(blk.conv2)], B, C, H, W, bias=blk.conv2.bias, res1=x, res2=res2, tile_stats=os_,
-                               out=ws.take(x.shape, dev), out_amax=out_amax)
+                               out=ws.take(x.shape, dev), out_amax=out_amax, pool=pool)
             for t in (img, y, ys, tab):
                 ws.give(t)
             return out, os_
@@ -968,6 +979,8 @@ class PUNetG(torch.nn.Module):
             finally:
                 if isinstance(shifts, _FieldShifts):
                     shifts.release()
+        if self.pool_route not in POOL_ROUTES:
+            raise ValueError(f"pool_route {self.pool_route!r}; choose from {POOL_ROUTES}")
         pk = self.packed_weights()
         ws = self._ws
         cfg = self.config
@@ -1043,10 +1056,17 @@ class PUNetG(torch.nn.Module):
                 ws.give(xe)
             skips = []
             for lv, blocks in enumerate(self.downward_blocks):                      # punetg.py:356-365
+                # pool_route: the DownSampler as a plain convolution of an already pooled tensor (a 3x3 fp16x3 packing only)
+                dpw = pk[id(self.downsamplers[lv].conv)]
+                plain_ds = (f == 2 and h3 and self.pool_route != "loader" and dpw.kind == "fp16x3" and dpw.ks == 3
+                            and dpw.subs is None)
+                pool = None
                 for j, blk in enumerate(blocks):
                     ha2 = slot(j == len(blocks) - 1)                                 # the level's last block feeds the DownSampler
                     nxt = blocks[j + 1] if j + 1 < len(blocks) else None             # ... and the skip: nobody normalises its result
-                    h2, hs2 = self._res(blk, h, sh(), pk, ws, xs=hs, out_amax=ha2,
+                    if j == len(blocks) - 1 and plain_ds and self.pool_route == "epilogue" and not (h.shape[2] % 2 or h.shape[3] % 2):
+                        pool = ops.PoolOut(ws.take((B, h.shape[1], h.shape[2] // 2, h.shape[3] // 2), dev))
+                    h2, hs2 = self._res(blk, h, sh(), pk, ws, xs=hs, out_amax=ha2, pool=pool,
                                         want_stats=self._consumes_stats(nxt, h.shape[1], h.shape[2], h.shape[3]))
                     give(h, hs)
                     h, hs, ha = h2, hs2, ha2
@@ -1056,7 +1076,20 @@ class PUNetG(torch.nn.Module):
                 ds = self.downsamplers[lv].conv
                 Ho, Wo = h.shape[2] // f, h.shape[3] // f
                 hs = stats_for(first_block_after_level(lv), ds.out_channels, Ho, Wo)
-                if f == 2:
+                hp = None
+                if pool is not None:                                                 # "epilogue": the last block's store phase pooled
+                    if pool.written:
+                        hp = pool.tensor
+                    else:
+                        ws.give(pool.tensor)                                         # ... or its launch did not qualify: the loader
+                elif plain_ds and self.pool_route == "pass":
+                    hp = ops.maxpool_f(h, 2, out=ws.take((B, h.shape[1], Ho, Wo), dev))
+                if hp is not None:
+                    # max |maxpool(h)| <= max |h| (below); the persistent kernel takes the raw-input launch where the shape is its own
+                    h = self._conv(ds, hp, pk, tile_stats=hs, out=ws.take((B, ds.out_channels, Ho, Wo), dev),
+                                   in_amax=amax_of(h, ha), pc_raw=True)
+                    ws.give(hp)
+                elif f == 2:
                     h = self._conv(ds, h, pk, load_mode=DS_LOAD_MAXPOOL2, tile_stats=hs,
                                    out=ws.take((B, ds.out_channels, Ho, Wo), dev), in_amax=amax_of(h, ha))
                 else:

@@ -1002,6 +1002,25 @@ def pack_conv(w, precision="bf16x6", upsampled=False):
     return PackedConv(pack_conv_weight(w), Cout, Cin, k, "fp32")
 
 
+class PoolOut:
+    """A place for MaxPool2d(2) of a convolution's result (conv2d / conv_img, pool=): tensor [B, Cout, H/2, W/2]; written is set by
+    the call -- True when the launch was one the persistent 3x3 kernel takes in its pooled form and the tensor holds the pooled
+    result, False when it was left untouched (the caller pools by other means).  The answer depends on shapes and switches only,
+    so it is the same at capture and at replay."""
+
+    def __init__(self, tensor):
+        self.tensor, self.written = tensor, False
+
+
+def _pool_out(pool, B, Cout, H, W, like):
+    if pool is None:
+        return None
+    if H % 2 or W % 2:
+        raise ValueError(f"pool: the convolution's output must have even sides; got {H}x{W}")
+    pool.written = False
+    return _out(pool.tensor, (B, Cout, H // 2, W // 2), like)
+
+
 def conv(x, pw, **kw):
     """Dispatch on the packing: ds_conv2d_h3, ds_conv2d_x6 or ds_conv2d; kernels larger than 3x3 as a sum of shifted
     3x3 blocks accumulated in place (the first launch carries bias / shift / residuals, the last one the statistics)."""
@@ -1009,6 +1028,8 @@ def conv(x, pw, **kw):
         return conv2d(x, pw.data, pw.Cout, pw.ks, kind=pw.kind, wshift=pw.wshift, w_up=pw.up, up_wshift=pw.up_wshift, **kw)
     if kw.get("res1_upsampled", False):
         raise NotImplementedError("res1_upsampled with kernels larger than 3x3")
+    if kw.pop("pool", None) is not None or kw.pop("pc_raw", False):
+        raise NotImplementedError("pool / pc_raw with kernels larger than 3x3")
     stats, out, out_amax = kw.pop("tile_stats", None), kw.pop("out", None), kw.pop("out_amax", None)
     first = dict(bias=kw.pop("bias", None), shift=kw.pop("shift", None), res1=kw.pop("res1", None), res2=kw.pop("res2", None))
     if kw.get("in_amax", None) is None and kw.get("prenorm", None) is None:
@@ -1260,16 +1281,21 @@ def gnorm1_stats_tiles(stats_a, kind, count, stats_b=None, eps=1e-5, stats=None)
 
 def conv2d(x, w_packed, Cout, ks, bias=None, shift=None, res1=None, res2=None,
            load_mode=N.DS_LOAD_PLAIN, out=None, kind="fp32", wshift=0, prenorm=None, tile_stats=None, circular=False,
-           res1_upsampled=False, w_up=None, up_wshift=0, tap_offset=None, in_amax=None, out_amax=None, amax_split=0):
+           res1_upsampled=False, w_up=None, up_wshift=0, tap_offset=None, in_amax=None, out_amax=None, amax_split=0,
+           pool=None, pc_raw=False):
     """'same' zero-padded conv; x [B, Cin, Hin, Win]; shift [1 or B, Cout] or None.
     fp16x3 kernels only: prenorm [B, ceil16(Cin), 4] (3x3) applies SiLU((x-M)*A+C) in the loader; tile_stats
     [B, Cout, conv_tile_count(H, W), 4] receives per-tile (K, sum(x-K), sum((x-K)^2), n) of the output;
     in_amax: int32 [B] per-sample max |x| (float bits) left by x's producer, NORMALISED for a norm + SiLU output, None = reduce
     x here (one extra read pass and an allocation: captured code passes slots); out_amax: zeroed int32 [B] slots that receive the
     per-sample max |out| for the next raw-input launch; amax_split (fp16x3 1x1 only): out_amax is [2, B] and channels >=
-    amax_split report to its second row (the attention in-projection: q, k | v)."""
+    amax_split report to its second row (the attention in-projection: q, k | v).
+    fp16x3 3x3, plain load only (ds_conv2d_h3_pc): pool = PoolOut that may receive MaxPool2d(2) of the result; pc_raw: a launch
+    without prenorm may take the persistent kernel."""
     B, Cin, Hin, Win = x.shape
     H, W = _load_sides(load_mode, (Hin, Win))
+    if pool is not None:
+        pool.written = False                                             # the kernels that have no pooled form leave it so
     if load_mode in (N.DS_LOAD_MAXPOOL2, N.DS_LOAD_AVGPOOL2):
         if (load_mode == N.DS_LOAD_AVGPOOL2) != (kind == "fp16x3" and ks == 1):
             raise ValueError("load modes: AVGPOOL2 is for the fp16x3 1x1 kernel, MAXPOOL2 for the others")
@@ -1320,6 +1346,18 @@ def conv2d(x, w_packed, Cout, ks, bias=None, shift=None, res1=None, res2=None,
                                         _p(res1), _p(res2), B, Cin, Cout, Hin, Win,
                                         (N.DS_PAD_CIRCULAR if circular else 0) | (N.DS_RES1_UPSAMPLED if res1_upsampled else 0),
                                         _p(prenorm), _p(tile_stats), pin, pout, _stream()), "ds_conv2d_h3_up")
+    elif kind == "fp16x3" and (pool is not None or pc_raw):
+        if load_mode != N.DS_LOAD_PLAIN:
+            raise ValueError("pool / pc_raw: plain-load convolutions")
+        pp = _pool_out(pool, B, Cout, H, W, x)
+        did = ctypes.c_int(0)
+        N.check(N.lib().ds_conv2d_h3_pc(_p(out), _p(x), _p(w_packed), int(wshift), _p(bias), _p(shift), stride,
+                                        _p(res1), _p(res2), B, Cin, Cout, H, W,
+                                        tap | (N.DS_PAD_CIRCULAR if circular else 0) | (N.DS_RES1_UPSAMPLED if res1_upsampled else 0),
+                                        _p(prenorm), _p(tile_stats), pin, pout, _stream(), _p(pp), ctypes.byref(did),
+                                        N.DS_PC_RAW if pc_raw else 0), "ds_conv2d_h3_pc")
+        if pool is not None:
+            pool.written = bool(did.value)
     elif kind == "fp16x3":
         N.check(N.lib().ds_conv2d_h3(_p(out), _p(x), _p(w_packed), int(wshift), _p(bias), _p(shift), stride,
                                      _p(res1), _p(res2), B, Cin, Cout, H, W,
@@ -1357,7 +1395,7 @@ def inorm_silu_images(x, w, b, kind, eps=1e-5, out=None):
 
 
 def conv_img(images, pw, B, Cin, H, W, bias=None, shift=None, res1=None, res2=None, tile_stats=None, out=None,
-             res1_upsampled=False, out_amax=None):
+             res1_upsampled=False, out_amax=None, pool=None):
     """3x3 'same' zero-padded fp16x3 convolution whose input is given as pre-split fp16 hi / lo images (the layout
     ds_inorm_silu_images writes): patches are staged by LDS-DMA, no split in the kernel.  pw = pack_conv(weight, "fp16x3")."""
     require_device(images, "images")
@@ -1372,6 +1410,15 @@ def conv_img(images, pw, B, Cin, H, W, bias=None, shift=None, res1=None, res2=No
     _residuals((B, Cout, H, W), None if res1_upsampled else res1, res2)
     _tile_stats(tile_stats, B, Cout, H, W)
     _entries(bias, Cout, "bias must have Cout entries")
+    if pool is not None:                                                  # pool: as conv2d's
+        pp = _pool_out(pool, B, Cout, H, W, images)
+        did = ctypes.c_int(0)
+        N.check(N.lib().ds_conv2d_h3_pc(_p(out), _p(images), _p(pw.data), int(pw.wshift), _p(bias), _p(shift), stride, _p(res1),
+                                        _p(res2), B, Cin, Cout, H, W, N.DS_RES1_UPSAMPLED if res1_upsampled else 0, None,
+                                        _p(tile_stats), None, _pi(out_amax, B, "out_amax"), _stream(), _p(pp), ctypes.byref(did),
+                                        N.DS_PC_IMAGES), "ds_conv2d_h3_pc")
+        pool.written = bool(did.value)
+        return out
     N.check(N.lib().ds_conv2d_h3_img(_p(out), _p(images), _p(pw.data), int(pw.wshift), _p(bias), _p(shift), stride, _p(res1),
                                      _p(res2), B, Cin, Cout, H, W, N.DS_RES1_UPSAMPLED if res1_upsampled else 0,
                                      _p(tile_stats), _pi(out_amax, B, "out_amax"), _stream()), "ds_conv2d_h3_img")

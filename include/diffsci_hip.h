@@ -236,6 +236,25 @@ int ds_conv2d_h3(float* out, const float* in, const void* w_packed, int wshift, 
                  const float* shift, int shift_stride, const float* res1, const float* res2,
                  int B, int Cin, int Cout, int H, int W, int load_mode,
                  const float* prenorm, float* tile_stats, const unsigned* in_amax, unsigned* out_amax, void* stream);
+/* ds_conv2d_h3 with a say in the kernel choice, and MaxPool2d(2) of the result as a second output (the DownSampler of PUNetG,
+ * commonlayers.py: MaxPool2d(2) then conv; the level's last residual block hands it the pooled tensor from its own store phase, and
+ * the DownSampler is then a plain raw-input convolution of a quarter of the pixels instead of a loader that reads four raw pixels per
+ * element once per output-channel tile).  Same arguments, same results bit for bit, then
+ *   pool_out [B, Cout, H/2, W/2] or NULL, 8-byte aligned, H and W even: receives max over each 2 x 2 window of out WHEN the launch
+ *            is one the persistent kernel (ds_conv3p.hip) takes in its pooled form -- fused-loader (prenorm) or image input, zero
+ *            padding, at least one of res1 / res2, no DS_RES1_UPSAMPLED, whole 8 x 32 tiles, Cin and Cout multiples of 64, at
+ *            least one (channel tile, pixel tile, sample) item per compute unit;
+ *   pooled   receives 1 if pool_out was written, else 0 (out is complete either way: the caller then pools by other means);
+ *            required with pool_out, may be NULL without;
+ *   flags    DS_PC_RAW: a launch without prenorm may take the persistent kernel too (otherwise only under DS_CONV_PC=3);
+ *            DS_PC_IMAGES: `in` is the pre-split image buffer of ds_conv2d_h3_img (prenorm and in_amax NULL; load_mode 0 or
+ *            DS_RES1_UPSAMPLED). */
+enum { DS_PC_RAW = 1, DS_PC_IMAGES = 2 };
+int ds_conv2d_h3_pc(float* out, const float* in, const void* w_packed, int wshift, const float* bias,
+                    const float* shift, int shift_stride, const float* res1, const float* res2,
+                    int B, int Cin, int Cout, int H, int W, int load_mode,
+                    const float* prenorm, float* tile_stats, const unsigned* in_amax, unsigned* out_amax, void* stream,
+                    float* pool_out, int* pooled, int flags);
 /* out[r] = max(out[r], bits(max |x[r*row_stride .. +n_per_row)|)): the in_amax of a tensor no epilogue produced (one read pass,
  * HBM-bound).  Merging semantics: zero the slots first; several calls accumulate (channel concatenations). */
 int ds_absmax_rows(unsigned* out, const float* x, int rows, size_t n_per_row, size_t row_stride, void* stream);

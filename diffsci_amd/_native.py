@@ -16,6 +16,7 @@ DS_LOAD_PLAIN, DS_LOAD_MAXPOOL2, DS_LOAD_UPSAMPLE2, DS_LOAD_AVGPOOL2 = 0, 1, 2, 
 DS_PAD_CIRCULAR = 16
 DS_RES1_UPSAMPLED = 32
 DS_PC_RAW, DS_PC_IMAGES = 1, 2
+DS_SI_BLEND, DS_SI_RENOISE = 1, 2
 
 
 class EvalCoef(Structure):
@@ -25,6 +26,12 @@ class EvalCoef(Structure):
                 ("one_minus_guidance", c_float), ("input_kind", c_int), ("stochastic", c_int),
                 ("scaled", c_int), ("scale", c_float), ("scale_mult", c_float), ("next_scale", c_float), ("xin_copies", c_int),
                 ("nonfinite", c_void_p)]
+
+
+class SIStep(Structure):
+    """struct ds_si_step."""
+    _fields_ = [(n, c_float) for n in ("score_a", "score_b", "score_den", "neg_half_omega", "dt", "noise_coef", "patch_alpha",
+                                       "patch_sigma", "jump_alpha", "jump_sigma", "c_in_next")]
 
 
 class NativeLibraryError(RuntimeError):
@@ -138,6 +145,12 @@ _PROTOS = {
     "ds_posterior_sample": (c_int, [_P, _P, _P, _P, c_uint64, c_uint64, c_int, c_size_t, c_int, c_float, c_float, _P]),
     "ds_box_copy3d": (c_int, [_P, _P, c_int, c_int, c_int, c_int, c_longlong, c_longlong, c_longlong, c_int, c_int, c_int,
                               c_int, c_int, c_int, c_int, c_int, c_int, _P]),
+    # (the flags word closes these two lists, as ds_conv2d_h3_pc's)
+    "ds_box_scatter3d": (c_int, [_P, _P, c_int, c_int, c_int, c_int, c_longlong, c_longlong, c_longlong, c_int, c_int, c_int,
+                                 c_int, c_int, c_int, c_int, c_int, c_int, _P, c_int]),
+    "ds_si_inpaint_counters": (c_uint64, [c_int, c_size_t, c_int]),
+    "ds_si_inpaint_step": (c_int, [_P, _P, _P, _P, _P, POINTER(EvalCoef), POINTER(SIStep), _P, _P, _P, _P, _P, _P, _P, c_uint64,
+                                   c_int, c_size_t, _P, c_int]),
     "ds_graph_begin_capture": (c_int, [_P]),
     "ds_graph_end_capture": (c_int, [_P, POINTER(_P), POINTER(c_int)]),
     "ds_graph_launch": (c_int, [_P, _P]),

@@ -452,8 +452,10 @@ class PlanCache:
     def clear(self):
         self.plans = {}
 
-    def run(self, key, make_loop, x, y=None, scale=None, eps=None, torch_graph=False):
-        """torch_graph: capture with torch.cuda.CUDAGraph instead of ops.Graph -- torch's allocator then serves allocations made
+    def run(self, key, make_loop, x, y=None, scale=None, eps=None, torch_graph=False, inputs=None):
+        """inputs: further per-run tensors of a loop that has them (siloop.SILoop: x_orig, mask), handed to loop.set_inputs
+        wherever x is loaded.
+        torch_graph: capture with torch.cuda.CUDAGraph instead of ops.Graph -- torch's allocator then serves allocations made
         inside the captured region from a pool the graph owns, which is what a run through user torch modules (extra_residual, an
         evaluated-as-given network) needs; our own capture refuses allocations instead (ops.Graph)."""
         if self.stream is None or self.stream.device != x.device:
@@ -467,6 +469,8 @@ class PlanCache:
             if plan is None:
                 loop = make_loop()
                 loop.load(x, scale)
+                if inputs is not None:
+                    loop.set_inputs(*inputs)
                 loop.set_noise(eps)
                 # eager warm-up: allocates the workspace, packs the weights, validates shapes.  Two steps, not the run (round 3: the
                 # first call of config 3 took 6.9 s, 3.2 s of them this pass): the first step visits both evaluation slots and every
@@ -499,6 +503,8 @@ class PlanCache:
                     refresh(y)
             loop, g = plan
             loop.load(x, scale)
+            if inputs is not None:
+                loop.set_inputs(*inputs)
             if not replay_same_noise:
                 loop.set_noise(eps)
             g.launch()

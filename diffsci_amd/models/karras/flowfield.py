@@ -24,6 +24,7 @@ from .engine import Loop, ModuleSource, PlanCache, condition_signature, model_si
 from . import edmbatchnorm
 from .karrasmodule import dict_to, dict_unsqueeze
 from .steptable import EvalRow, StepRow, StepTable
+from . import siloop
 
 
 class SIScheduler(object):
@@ -514,6 +515,121 @@ class SIModule(torch.nn.Module):
                             x = ops.axpby(x, float(c.alpha_fn(t_curr)), randn_like(x), float(c.sigma_fn(t_curr)))
                             x = blend(x, t_curr)
             return self.initial_norm.unnorm(x)
+
+    # ------------------------------------------------------------------ the fused, captured Euler-Maruyama runs
+    def _run_si_table(self, table, x, y, guidance, integrate_on_sigma, scale, inputs, draws):
+        """One run of a siloop.SITable from the start noise x: one network evaluation and one fused step kernel per row
+        (ds_inpaint.hip), captured once per plan key and replayed with x, the known data, the mask, the condition's values and
+        the noise (the draws, or the Philox offset) refreshed.  draws: None (in-kernel Philox seeded from torch's generator) or
+        the list of injected draws."""
+        injected = draws is not None
+        checked = [False]
+
+        def run():
+            src = self._source(y, guidance, x)
+            checked[0] = src.nonfinite_word is not None and len(table.rows) > 0
+            make = lambda: siloop.SILoop(table, src, x, injected_noise=injected)     # noqa: E731
+            if self.use_graph and x.is_cuda and (src.planned or self.capture_eager):
+                src.static_condition = not src.planned
+                key = (table.kind, src.planned, tuple(x.shape), table.digest(), float(guidance), condition_signature(y),
+                       bool(integrate_on_sigma), injected, str(x.device), model_signature(self.model))
+                return self._plans.run(key, make, x, y=y, scale=scale, eps=draws, torch_graph=not src.planned, inputs=inputs)
+            loop = make()
+            loop.load(x, scale)
+            loop.set_inputs(*inputs)
+            loop.set_noise(draws)
+            loop.launch()
+            return loop.result()
+
+        out = run()
+        if precision.needs_escalation(self.model, out, x, result_checked=checked[0]):
+            precision.escalate(self.model)
+            out = run()
+        return self.initial_norm.unnorm(out)
+
+    @staticmethod
+    def _take_draws(noise, table, x_shape):
+        """The draws a run of `table` consumes, taken from the iterator in order and checked (None: none injected)."""
+        if noise is None:
+            return None
+        out = []
+        for r in table.rows:
+            for i in range(r.draws):
+                e = next(noise)
+                want = tuple(x_shape) if i % 2 == 0 else (1,) + tuple(x_shape[1:])
+                if tuple(e.shape) != want:
+                    raise ValueError(f"injected noise has shape {tuple(e.shape)}, expected {want}")
+                out.append(e)
+        return out
+
+    @ops.device_guard
+    def inpaint_fused(self, x_orig, mask, nsamples: int = 1, y=None, guidance: float = 1.0, nsteps: int = 30,
+                      integrate_on_sigma: bool = False, noise_injection: bool = False, orig_noise=None,
+                      mask_falloff: int = 0, resample_steps: int = 0, jump_length: int = 1, mask_start_t: float = 1.0,
+                      noise=None):
+        """`inpaint` (same arguments, same result given the same draws) on the fused step kernel and a captured run: one
+        launch per inner iteration after the network call, the network conditioning tabulated once per run, the whole run a
+        hipGraph replayed for every call of the same shape and schedule.  Without `noise` the draws come from the in-kernel
+        Philox stream seeded from torch's CUDA generator (reproducible from torch.manual_seed; consecutive calls draw disjoint
+        ranges) -- not the values torch.randn_like would give.  Preconditioners that cannot be tabulated run `inpaint`."""
+        if self.config.preconditioner.generic:
+            return self.inpaint(x_orig, mask, nsamples, y, guidance, nsteps, integrate_on_sigma, noise_injection, orig_noise,
+                                mask_falloff, resample_steps, jump_length, mask_start_t, noise)
+        warnings.warn("We are assuming we are in latent space for inpainting")
+        draws = iter(noise) if noise is not None else None
+        with torch.inference_mode():
+            if y is not None:
+                warnings.warn("Moving y to device: {}".format(self.device))
+                y = dict_to(y, self.device)
+            x_orig = x_orig.to(self.device)
+            mask = mask.to(self.device)
+            shape = x_orig.shape
+            soft_mask = (self._create_soft_mask(mask, mask_falloff) if mask_falloff > 0 else mask).to(torch.float32).contiguous()
+            x_orig = self.initial_norm(x_orig.unsqueeze(0).contiguous())
+            if orig_noise is None:
+                x = torch.randn(nsamples, *shape).to(self.device)
+            else:
+                assert orig_noise.shape[0] == nsamples, "Number of samples must match"
+                assert orig_noise.shape[1:] == shape, "Shape of noise must match"
+                x = orig_noise.to(self.device)
+            table = siloop.inpaint_table(self.config, nsteps, integrate_on_sigma, resample_steps, jump_length, mask_start_t)
+            x = x.contiguous()
+            ops.require_device(x, "x")
+            return self._run_si_table(table, x, y, guidance, integrate_on_sigma, float(self.config.sigma_fn(table.t[0])),
+                                      (x_orig, soft_mask), self._take_draws(draws, table, x.shape))
+
+    @ops.device_guard
+    def sample_fused(self, nsamples: int, shape: list[int], y=None, guidance: float = 1.0, nsteps: int = 30,
+                     is_latent_shape: bool = False, integrate_on_sigma: bool = False, noise_injection: bool = False,
+                     return_latents: bool = False, orig_noise=None, noise=None):
+        """`sample` with its noise_injection=True branch (Euler-Maruyama, eager in `sample`) on the fused step kernel and a
+        captured run, as inpaint_fused.  noise: an iterator of the draws in the reference's order -- the start noise
+        [nsamples, *shape] when orig_noise is None, then one [nsamples, *shape] per step.  Everything else (the deterministic Heun
+        run, already captured; preconditioners that cannot be tabulated; a pixel-space shape with an autoencoder) runs `sample`."""
+        draws = iter(noise) if noise is not None else None
+        if orig_noise is None and draws is not None:
+            orig_noise = next(draws)
+        if not noise_injection or self.config.preconditioner.generic or (not is_latent_shape and self.autoencoder):
+            return self.sample(nsamples, shape, y, guidance, nsteps, is_latent_shape, integrate_on_sigma, noise_injection,
+                               return_latents, orig_noise)
+        with torch.inference_mode():
+            if orig_noise is None:
+                x = torch.randn(nsamples, *shape).to(self.device)
+            else:
+                assert orig_noise.shape[0] == nsamples, "Number of samples must match"
+                assert list(orig_noise.shape[1:]) == list(shape), "Shape of noise must match"
+                x = orig_noise.to(self.device)
+            if y is not None:
+                warnings.warn("Moving y to device: {}".format(self.device))
+                y = dict_unsqueeze(dict_to(y, self.device), 0)
+            table = siloop.em_table(self.config, torch.linspace(1, 0, nsteps), integrate_on_sigma)
+            x = x.contiguous()
+            ops.require_device(x, "x")
+            x = self._run_si_table(table, x, y, guidance, integrate_on_sigma, float(self.config.sigma_fn(table.t[0])), (),
+                                   self._take_draws(draws, table, x.shape))
+            if not return_latents:
+                x, _ = self.decode(x, y)
+            return x
 
     def _em_step(self, x, tc, tn, y, guidance, integrate_on_sigma, randn_like):
         """The Euler-Maruyama branch of integration_step (flowfield.py:783-793) with an injectable noise source."""

@@ -1,6 +1,7 @@
 """Tensor-level wrappers over the C ABI: shape / dtype / device checks on the host, then a raw
 pointer + stream call.  PyTorch is used only as the owner of device memory and of the stream."""
 import ctypes
+import gc
 
 import torch
 
@@ -451,6 +452,69 @@ def euler(x, f, k, dt, fu=None, x_out=None, xin_out=None, c_in_next=1.0, eps=Non
     N.check(N.lib().ds_karras_euler(_p(x_out), _p(xin_out), _p(x), _p(f), _p(fu), ctypes.byref(k),
                                     float(dt), float(c_in_next), _p(eps), ps, po, float(noise_coef),
                                     float(sqrt_abs_dt), n, _stream()), "ds_karras_euler")
+    return x_out
+
+
+def _overlap(a, b):
+    """Do two tensors share bytes?  (contiguous tensors: their address ranges)"""
+    if a is None or b is None or not a.numel() or not b.numel():
+        return False
+    pa, pb = a.data_ptr(), b.data_ptr()
+    return pa < pb + b.numel() * b.element_size() and pb < pa + a.numel() * a.element_size()
+
+
+def si_inpaint_counters(B, n, blend=False, renoise=False):
+    """Philox counters one si_inpaint_step launch consumes (ds_si_inpaint_counters: the step's [B, n], with the blend the
+    patch's [n], with the jump both again).  Host arithmetic of the library: no launch."""
+    flags = (N.DS_SI_BLEND if blend or renoise else 0) | (N.DS_SI_RENOISE if renoise else 0)
+    return int(N.lib().ds_si_inpaint_counters(int(B), int(n), flags))
+
+
+def si_inpaint_step(x, f, k, s, fu=None, x_orig=None, mask=None, blend=False, renoise=False, eps=None, philox=None, x_out=None,
+                    xin_out=None):
+    """One inner iteration of SIModule.inpaint after the network call, fused (ds_inpaint.hip): the Euler-Maruyama step under
+    k (EvalCoef) and s (SIStep), with blend the known region x_orig [n] re-imposed under mask [n], with renoise the jump back
+    and its blend; x [B, n...] -> x_out (may be x itself) and xin_out = c_in_next * result (k.xin_copies copies).  Noise: eps =
+    (step [B, n], patch [n], jump [B, n], jump patch [n]) as far as the mode draws, or philox = (state, offset).  ValueError
+    before any launch for sizes that disagree, a missing draw, outputs that overlap an input."""
+    if renoise and not blend:
+        raise ValueError("si_inpaint_step: renoise goes with blend")
+    if (eps is None) == (philox is None):
+        raise ValueError("si_inpaint_step: give injected eps or a Philox state, exactly one")
+    if x_out is None and xin_out is None:
+        raise ValueError("si_inpaint_step: no output requested")
+    B = x.shape[0] if x.dim() else 0
+    n = _same_numel(x, f, fu, x_out)
+    nps = n // B if B else 0
+    if B < 1 or nps < 1:
+        raise ValueError(f"si_inpaint_step: empty state {tuple(x.shape)}")
+    _xin_numel(x, xin_out, k.xin_copies)
+    if blend:
+        if x_orig is None or mask is None or x_orig.numel() != nps or mask.numel() != nps:
+            raise ValueError(f"si_inpaint_step: x_orig and mask must hold one sample ({nps} elements)")
+    else:
+        x_orig = mask = None
+    draws = [None] * 4
+    if eps is not None:
+        want = 4 if renoise else (2 if blend else 1)
+        eps = tuple(eps)
+        if len(eps) < want or any(e is None for e in eps[:want]):
+            raise ValueError(f"si_inpaint_step: this mode reads {want} injected draws; got {len(eps)}")
+        for i in range(want):
+            if eps[i].numel() != (n if i % 2 == 0 else nps):
+                raise ValueError(f"si_inpaint_step: draw {i} holds {eps[i].numel()} elements; expected {n if i % 2 == 0 else nps}")
+            draws[i] = eps[i]
+    ins = [t for t in (f, fu, x_orig, mask) + tuple(draws) if t is not None]
+    if x_out is not None and x_out.data_ptr() != x.data_ptr() and _overlap(x_out, x):
+        raise ValueError("si_inpaint_step: x_out overlaps x (it may only be x itself)")
+    if any(_overlap(x_out, t) for t in ins) or any(_overlap(xin_out, t) for t in ins + [x, x_out]):
+        raise ValueError("si_inpaint_step: an output overlaps an input")
+    ps, po = _philox(philox)
+    flags = (N.DS_SI_BLEND if blend else 0) | (N.DS_SI_RENOISE if renoise else 0)
+    ptrs = [_p(t, what) for t, what in ((x_out, "x_out"), (xin_out, "xin_out"), (x, "x"), (f, "f"), (fu, "fu"), (x_orig, "x_orig"),
+                                        (mask, "mask"))] + [_p(e, "eps") for e in draws]
+    N.check(N.lib().ds_si_inpaint_step(*ptrs[:5], ctypes.byref(k), ctypes.byref(s), *ptrs[5:], ps, po, B, nps, _stream(), flags),
+            "ds_si_inpaint_step")
     return x_out
 
 
@@ -1233,6 +1297,42 @@ def box_copy3d(src, src_start, dst, dst_start, size):
     return dst
 
 
+def box_scatter3d(src, src_start, dst, dst_start, size):
+    """dst[..., (d0+i) % D0, (d1+j) % D1, (d2+k) % D2] = src[..., s0+i, s1+j, s2+k] for 0 <= (i, j, k) < size, plane by plane
+    (ds_window.hip): the counterpart of box_copy3d with the periodic side the destination (torchutils.py:238-309,
+    periodic_setitem).  The source box must lie inside src; a destination start may be negative.  ValueError before any launch:
+    what box_copy3d refuses, a source box outside src, and a box longer than a destination axis -- a write of more than one
+    period, which periodic_setitem refuses too.  An empty box launches nothing.  Returns dst."""
+    for t, what in ((src, "src"), (dst, "dst")):
+        if not isinstance(t, torch.Tensor):
+            raise TypeError(f"box_scatter3d: {what} must be a torch.Tensor")
+        if t.dtype != torch.float32:
+            raise ValueError(f"box_scatter3d: {what} has dtype {t.dtype}; the copy is fp32 only")
+        if t.dim() < 3:
+            raise ValueError(f"box_scatter3d: {what} needs at least three axes; got {tuple(t.shape)}")
+    s, d, L = _triple(src_start, "src_start"), _triple(dst_start, "dst_start"), _triple(size, "size")
+    S, D = tuple(src.shape[-3:]), tuple(dst.shape[-3:])
+    if min(S) < 1 or min(D) < 1:
+        raise ValueError(f"box_scatter3d: empty spatial axes (src {S}, dst {D})")
+    planes = src.numel() // (S[0] * S[1] * S[2])
+    if planes != dst.numel() // (D[0] * D[1] * D[2]):
+        raise ValueError(f"box_scatter3d: src {tuple(src.shape)} and dst {tuple(dst.shape)} hold different numbers of planes")
+    if min(L) < 0 or any(a < 0 or a + n > m for a, n, m in zip(s, L, S)):
+        raise ValueError(f"box_scatter3d: source box start {s} size {L} leaves src {S}")
+    if any(n > m for n, m in zip(L, D)):
+        raise ValueError(f"box_scatter3d: box {L} is longer than a destination axis {D}: a periodic write of more than one period")
+    if src.untyped_storage().data_ptr() == dst.untyped_storage().data_ptr() and src.numel() and dst.numel():
+        raise ValueError("box_scatter3d: src and dst share storage")
+    if max(S + D) >= 1 << 31 or L[0] * L[1] >= (1 << 31) - (1 << 20) or planes >= 1 << 31:
+        raise ValueError(f"box_scatter3d: axes beyond 31 bits (src {S}, dst {D}, box {L})")
+    ps, pd = _p(src, "src"), _p(dst, "dst")
+    if planes == 0 or min(L) == 0:
+        return dst
+    N.check(N.lib().ds_box_scatter3d(pd, ps, planes, D[0], D[1], D[2], d[0], d[1], d[2], S[0], S[1], S[2], s[0], s[1], s[2],
+                                     L[0], L[1], L[2], _stream(), 0), "ds_box_scatter3d")
+    return dst
+
+
 def conv_tile_count(H, W):
     """Pixel tiles per channel plane in the fp16x3 kernels' tile_stats layout."""
     return N.lib().ds_conv_tile_count(int(H), int(W))
@@ -1725,13 +1825,27 @@ class Graph:
 
     def __enter__(self):
         self._stream = _stream()
-        self._alloc0 = self._allocations()
-        N.check(N.lib().ds_graph_begin_capture(self._stream), "ds_graph_begin_capture")
+        # No finaliser may run inside the captured region: a module that has captured plans is cyclic garbage once dropped
+        # (module -> plans -> loop -> source -> module), and the collector frees its graphs and tensors -- HIP calls on the
+        # capturing thread -- whenever its counters say so.  Collect now, and keep the collector off until the capture ends
+        # (torch.cuda.graph collects before it captures for the same reason).
+        self._gc = gc.isenabled()
+        gc.collect()
+        gc.disable()
+        try:
+            self._alloc0 = self._allocations()
+            N.check(N.lib().ds_graph_begin_capture(self._stream), "ds_graph_begin_capture")
+        except BaseException:
+            if self._gc:
+                gc.enable()
+            raise
         return self
 
     def __exit__(self, et, ev, tb):
         n = ctypes.c_int(0)
         rc = N.lib().ds_graph_end_capture(self._stream, ctypes.byref(self._h), ctypes.byref(n))
+        if self._gc:
+            gc.enable()
         if et is None:
             N.check(rc, "ds_graph_end_capture")
             # The graph bakes device addresses.  A tensor allocated inside the captured region belongs to torch's

@@ -679,6 +679,45 @@ int ds_posterior_sample(float* out, const float* moments, const float* eps, cons
 int ds_box_copy3d(float* dst, const float* src, int planes, int S0, int S1, int S2, long long s0, long long s1, long long s2, int D0,
                   int D1, int D2, int d0, int d1, int d2, int L0, int L1, int L2, void* stream);
 
+/* The scatter counterpart: the box lies inside src, the destination is periodic,
+ *   dst[n, (d0+i) mod D0, (d1+j) mod D1, (d2+k) mod D2] = src[n, s0+i, s1+j, s2+k]    0 <= i < L0, j < L1, k < L2, n < planes
+ * dst [planes, D0, D1, D2], src [planes, S0, S1, S2], both dense; a destination start may be negative.  A box longer than a
+ * destination axis (a write of more than one period: which copy wins?) and a source box outside src are DS_ERR_SHAPE: nothing is
+ * launched.  src and dst must not overlap.  An empty box launches nothing.  Element offsets are 64-bit; L0 * L1 < 2^31.
+ * flags: 0 (none defined; the word closes the list as ds_conv2d_h3_pc's does). */
+int ds_box_scatter3d(float* dst, const float* src, int planes, int D0, int D1, int D2, long long d0, long long d1, long long d2,
+                     int S0, int S1, int S2, int s0, int s1, int s2, int L0, int L1, int L2, void* stream, int flags);
+
+/* ------------------------------------------------------------------------------------
+ * The Euler-Maruyama inpainting step of the stochastic-interpolant sampler (flowfield.py:546-641, 783-793): everything one inner
+ * iteration of SIModule.inpaint does after the network call, in one pass.  x, f, fu, x_out [B, n]; x_orig, mask [n], shared by
+ * the batch.  With v = the drift of (x, f[, fu]) under k (ds_karras_drift's arithmetic):
+ *   score = (score_a*v + score_b*x) / score_den                 score_a = alpha, score_b = -alpha', den = sigma*(alpha'*sigma - alpha*sigma')
+ *   x1    = (x + dt*(v + neg_half_omega*score)) + noise_coef*eps_step
+ *   DS_SI_BLEND:    x1 = x1*(1 - mask) + (patch_alpha*x_orig + patch_sigma*eps_patch)*mask                 (ds_mask_blend's arithmetic)
+ *   DS_SI_RENOISE:  x1 = jump_alpha*x1 + jump_sigma*eps_jump, then the blend again with (jump_alpha, jump_sigma, eps_jump_patch)
+ *   x_out = x1 (may alias x; may be NULL);  xin_out = c_in_next * x1 (may be NULL; k->xin_copies copies; aliases nothing)
+ * eps_step, eps_jump [B, n] and eps_patch, eps_jump_patch [n] are read when eps_step != NULL; otherwise philox_state (device
+ * memory, (seed, base)) is required and the draws come from ds_philox_normal's stream at counters philox_offset + (0, cB,
+ * cB + c1, 2*cB + c1), cB = ceil(B*n/4), c1 = ceil(n/4): the order in which the reference draws them.  ds_si_inpaint_counters
+ * returns what one launch with these flags consumes.  k->nonfinite as in ds_karras_euler.  n % 4 == 0 and 16-byte aligned
+ * pointers take 16-byte accesses, anything else the element-wise path. */
+typedef struct ds_si_step {
+  float score_a, score_b, score_den;
+  float neg_half_omega; /* -(0.5*omega), omega = sigma(t) */
+  float dt;
+  float noise_coef;     /* sqrt(omega*|dt|) */
+  float patch_alpha, patch_sigma; /* alpha, sigma at the step's end */
+  float jump_alpha, jump_sigma;   /* alpha, sigma at the step's start (the jump back) */
+  float c_in_next;
+} ds_si_step;
+enum { DS_SI_BLEND = 1, DS_SI_RENOISE = 2 };
+uint64_t ds_si_inpaint_counters(int B, size_t n_per_sample, int flags);
+int ds_si_inpaint_step(float* x_out, float* xin_out, const float* x, const float* f, const float* fu, const ds_eval_coef* k,
+                       const ds_si_step* s, const float* x_orig, const float* mask, const float* eps_step, const float* eps_patch,
+                       const float* eps_jump, const float* eps_jump_patch, const uint64_t* philox_state, uint64_t philox_offset,
+                       int B, size_t n_per_sample, void* stream, int flags);
+
 /* ------------------------------------------------------------------------------------
  * hipGraph capture of a launch sequence (the whole N-step loop is captured once per
  * (network, nsteps, batch) and replayed).

@@ -463,3 +463,25 @@ def test_condition_copies_keep_structure_and_follow_values():
     ct = clone_condition(t)
     copy_condition(ct, t * 2)
     assert torch.equal(ct, t * 2) and clone_condition(None) is None
+
+
+def test_grid_caps_mirror_the_kernel_sources():
+    """tests/test_gpu_grid_caps.py sizes its cases just past the grid caps of the streaming kernels and proves it from constants;
+    every constant still reads what the kernel source says, so who changes a cap is sent to those shapes."""
+    import re
+    from tests import test_gpu_grid_caps as caps
+    texts = {}
+    for name, value, fname, pattern in caps.CAP_SOURCES:
+        if fname not in texts:
+            with open(os.path.join(caps.CSRC, fname)) as fh:
+                texts[fname] = fh.read()
+        found = re.findall(pattern, texts[fname])
+        assert len(found) == 1, (name, fname, pattern, found)                # one line decides the cap
+        groups = found[0] if isinstance(found[0], tuple) else (found[0],)
+        assert all(int(v) == value for v in groups), (name, fname, groups, value)
+        assert getattr(caps, name) == value
+    assert caps.T == caps.GRID_FOR * caps.THREADS == 524288
+    # the flat sizes of the stepper cases follow from the constants; every cap constant of the module is named in CAP_SOURCES
+    assert caps.N_A == 2752512 and caps.N_A // 4 > caps.T and caps.N_B % 4 == 3
+    assert {n for n, *_ in caps.CAP_SOURCES} == {k for k in vars(caps) if k.isupper() and isinstance(getattr(caps, k), int)} - \
+        {"T", "N_A", "N_B"}

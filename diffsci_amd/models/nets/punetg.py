@@ -208,6 +208,25 @@ class _ConditionDrop(torch.nn.Module):
             self.register_buffer("null_embedding", torch.zeros(1, hidden_dim))
 
 
+def corner_pool_factor(field, block):
+    """ResnetBlockC.rescale_yt (commonlayers.py:838-869) as a rule: a field of time embeddings with sides `field` serves a block
+    with sides `block` through the top-left corner of every window of f pixels a side (CornerPool) -> f, 1 for equal sides.  The
+    factor comes from the first side; every side must satisfy block * f == field.  A coarser field takes the reference through
+    torch.nn.Upsample(shape_factor), whose first argument is the output size -- it fails there unless the block's side equals
+    the factor; not reproduced."""
+    field, block = tuple(field), tuple(block)
+    if len(field) == len(block):
+        if field == block:
+            return 1
+        if field[0] <= block[0]:
+            raise NotImplementedError("a conditional-embedding field coarser than a block's resolution (the reference's "
+                                      "upscaling branch passes the factor as torch.nn.Upsample's size and fails as well)")
+        f = field[0] // block[0]
+        if all(d * f == s for d, s in zip(block, field)):
+            return f
+    raise ValueError(f"yt_dims {field} and y_dims {block} are not compatible")
+
+
 class _FieldShifts:
     """Per-pixel time shifts, computed where they are used.  A field-valued conditional embedding makes the time embedding a
     field te [B, C, He, We] (punetg.py:405-410) and every block's ResnetTimeBlock a per-pixel MLP (commonlayers.py:537-546)
@@ -225,45 +244,24 @@ class _FieldShifts:
         self.am = AmaxArena(ws, self.batch, te.device) if h3 else None
         self.levels = {}
 
-    def _level_nd(self, dims):
-        """The volume form of `level`: one ds_cornerpool_f launch per resolution writes te + ye there and leaves its amax row.
-        The reference's rule (rescale_yt): the factor comes from the first side, every side must satisfy block * f == field."""
-        sp = tuple(self.te.shape[2:])
-        if len(dims) != len(sp):
-            raise ValueError(f"yt_dims {sp} and y_dims {dims} are not compatible")
-        if sp != dims and sp[0] <= dims[0]:
-            raise NotImplementedError("a conditional-embedding field coarser than a block's resolution (the reference's "
-                                      "upscaling branch passes the factor as torch.nn.Upsample's size and fails as well)")
-        f = sp[0] // dims[0]
-        if any(d * f != s for d, s in zip(dims, sp)):
-            raise ValueError(f"yt_dims {sp} and y_dims {dims} are not compatible")
-        a = self.am.row() if self.am is not None else None
-        t = ops.cornerpool_f(self.te, f, te=self.rows, out_amax=a,
-                             out=self.ws.take((self.batch, self.te.shape[1]) + dims, self.te.device))
-        return t, a, True
-
     def level(self, *dims):
         """te at a block's resolution -- level(H, W) -> [B, C, H, W], level(D, H, W) -> [B, C, D, H, W] -- and its amax row
         (fp16x3)."""
         dims = tuple(int(v) for v in dims)
         got = self.levels.get(dims)
-        if got is None and (self.te.dim() != 4 or len(dims) != 2):
-            got = self.levels[dims] = self._level_nd(dims)
         if got is None:
-            H, W = dims
-            B, C, h, w = self.te.shape
-            if (h, w) == (H, W):
-                t, owned = self.te, False
-            elif h > H:
-                f = h // H
-                if H * f != h or W * f != w:
-                    raise ValueError(f"yt_dims {(h, w)} and y_dims {(H, W)} are not compatible")
-                t, owned = self.ws.take((B, C, H, W), self.te.device), True
-                t.copy_(self.te[:, :, ::f, ::f])                      # CornerPool2d(f): the top-left corner of every window
+            f = corner_pool_factor(self.te.shape[2:], dims)
+            if self.te.dim() == 5:           # volumes: one ds_cornerpool_f launch per resolution writes te + ye there and leaves its amax row
+                a = self.am.row() if self.am is not None else None
+                t = ops.cornerpool_f(self.te, f, te=self.rows, out_amax=a,
+                                     out=self.ws.take((self.batch, self.te.shape[1]) + dims, self.te.device))
             else:
-                raise NotImplementedError("a conditional-embedding field coarser than a block's resolution (the reference's "
-                                          "upscaling branch passes the factor as torch.nn.Upsample's size and fails as well)")
-            got = self.levels[(H, W)] = (t, self.am.of(t) if self.am is not None else None, owned)
+                t = self.te
+                if f > 1:
+                    t = self.ws.take(tuple(self.te.shape[:2]) + dims, self.te.device)
+                    t.copy_(self.te[:, :, ::f, ::f])                  # CornerPool2d(f): the top-left corner of every window
+                a = self.am.of(t) if self.am is not None else None
+            got = self.levels[dims] = (t, a, t is not self.te)
         return got[0], got[1]
 
     def release(self):
@@ -299,17 +297,14 @@ class PUNetG(torch.nn.Module):
         # workspace buffer and the plain convolution after it
         self.factor = scale_factor(config.transition_scale_factor)
         mc = config.model_channels
-        mult = config.extended_channel_expansion
         self.time_projection = _Fourier(mc, config.time_projection_scale)
         self.conditional_embedding = conditional_embedding
         self.cond_drop = (_ConditionDrop(config.cond_drop, mc, config.cond_drop_learnable)
                           if config.cond_drop is not None and config.cond_drop > 0 else None)     # punetg.py:102-106
         self.circular = config.convolution_type == "circular"
-        circ = config.convolution_type                     # conv kind: "default" | "circular" | "mp"
         self.mp = config.convolution_type == "mp"
         self.cosine_attn = config.attn_type == "cosine"
         self.inhouse_attn = self.mp or self.cosine_attn        # attention.py:29-52
-        hb = bool(config.bias)
         norms = (config.first_resblock_norm, config.second_resblock_norm)
         self.norm_kinds = tuple(NORM_KINDS.get(n, 2) for n in norms)
         # bias=False: no convolution biases; a constant-one input channel is appended instead (punetg.py:190-191,390-394)
@@ -843,7 +838,8 @@ class PUNetG(torch.nn.Module):
             return got
         yt = None
         if shift is not None and shift.dim() == 4:         # the same, handed over as a tensor [B, C, He, We]
-            yt, shift = self._rescale_shift_field(shift, H, W), None
+            f = corner_pool_factor(shift.shape[2:], (H, W))
+            yt, shift = (shift if f == 1 else shift[:, :, ::f, ::f].contiguous()), None
         return self._res_body(blk, x, shift, yt, pk, ws, res2, xs, want_stats, out_amax, pool)
 
     def _res_body(self, blk, x, shift, yt, pk, ws, res2, xs, want_stats, out_amax, pool=None):
@@ -937,425 +933,120 @@ class PUNetG(torch.nn.Module):
         degrading gracefully to 2^-25 absolute) for any input magnitude.  Checked on the host once per parameter version."""
         return precision.norms_in_window(self._window_cache, id(blk), (blk.gnorm1, blk.gnorm2))
 
-    def _table_images_ok(self, blk, C, k1, k2):
-        """As _norm_images_ok for the table route (any plane size; GroupLN / GroupRMS / no norm)."""
+    def _images_ok(self, blk, C, k1, k2, kinds):
+        """The norms of this block (kinds k1, k2 among `kinds`) can hand their convolutions pre-split images: fp16x3 3x3
+        convolutions with zero padding that keep the channel count, an even number of 16-channel chunks."""
         return (getattr(self, "norm_images", True) and self.conv_precision == "fp16x3" and not self.circular
-                and self.config.kernel_size == 3 and k1 in (0, 1, 2) and k2 in (0, 1, 2) and ((C + 15) // 16) % 2 == 0
+                and self.config.kernel_size == 3 and k1 in kinds and k2 in kinds and ((C + 15) // 16) % 2 == 0
                 and blk.conv1.out_channels == C and blk.conv2.out_channels == C)
 
-    def _norm_images_ok(self, blk, C, H, W, k1, k2):
-        """The standalone norms of this block can hand their convolutions pre-split images: fp16x3 3x3 convolutions with zero
-        padding that keep the channel count, an even number of 16-channel chunks, GroupLN / GroupRMS, planes the image kernel
-        takes."""
-        return (getattr(self, "norm_images", True) and self.conv_precision == "fp16x3" and not self.circular
-                and self.config.kernel_size == 3 and k1 in (0, 1) and k2 in (0, 1) and ((C + 15) // 16) % 2 == 0
-                and blk.conv1.out_channels == C and blk.conv2.out_channels == C and ops.inorm_silu_images_supported(H, W))
+    def _table_images_ok(self, blk, C, k1, k2):
+        """The table route: any plane size; GroupLN / GroupRMS / no norm."""
+        return self._images_ok(blk, C, k1, k2, (0, 1, 2))
 
-    @staticmethod
-    def _rescale_shift_field(yt, H, W):
-        """ResnetBlockC.rescale_yt (commonlayers.py:838-869): the top-left corner of every window (CornerPool2d) when the
-        field is finer than the block.  A coarser field takes the reference through torch.nn.Upsample(shape_factor), whose
-        first argument is the output size -- it fails there unless the block's side equals the factor; not reproduced."""
-        h, w = yt.shape[2:]
-        if (h, w) == (H, W):
-            return yt
-        if h > H:
-            f = h // H
-            if H * f != h or W * f != w:
-                raise ValueError(f"yt_dims {(h, w)} and y_dims {(H, W)} are not compatible")
-            return yt[:, :, ::f, ::f].contiguous()
-        raise NotImplementedError("a conditional-embedding field coarser than a block's resolution (the reference's "
-                                  "upscaling branch passes the factor as torch.nn.Upsample's size and fails as well)")
+    def _norm_images_ok(self, blk, C, H, W, k1, k2):
+        """The standalone norms writing images themselves: GroupLN / GroupRMS, planes the image kernel takes."""
+        return self._images_ok(blk, C, k1, k2, (0, 1)) and ops.inorm_silu_images_supported(H, W)
 
     def forward_with_shifts(self, x, shifts, row=None, out=None):
         """UNet body given the per-block time shifts.  shifts[k] is [M, C_k]; row selects one row
         shared by the whole batch (sampling: sigma is a per-step constant), row=None means one row
-        per sample (M == B).  Every activation travels with the tile statistics its producer left."""
+        per sample (M == B); or a field of shifts (`field_shifts`), given back here.  Fields [B, C, H, W] and volumes
+        [B, C, D, H, W] take the same walk; what it launches is the dimension's answer (`_Fields`, `_Volumes`)."""
         require_eval(self, self.config.dropout, self.config.cond_dropout, self.config.cond_drop)
         self.check_field_size(x.shape)
-        if self.dim == 3:
-            try:
-                return self._forward3d(x, shifts, row=row, out=out)
-            finally:
-                if isinstance(shifts, _FieldShifts):
-                    shifts.release()
-        if self.pool_route not in POOL_ROUTES:
-            raise ValueError(f"pool_route {self.pool_route!r}; choose from {POOL_ROUTES}")
-        pk = self.packed_weights()
-        ws = self._ws
-        cfg = self.config
-        f = self.factor
-        B = x.shape[0]
-        dev = x.device
-        lazy_shifts = shifts if isinstance(shifts, _FieldShifts) else None
-        it = iter(range(len(shifts))) if lazy_shifts is None else None
-
-        def sh():
-            if lazy_shifts is not None:                # per-pixel shifts: each block evaluates its own (_field_shift)
-                return lazy_shifts
-            return shift_rows(shifts[next(it)], row, B)    # a field handed over as a tensor allocates: not for captured runs
-
-        def give(t, ts):
-            ws.give(t)
-            if ts is not None:
-                ws.give(ts)
-
-        # Activation exponents (ops.py): every launch that reads a tensor which no norm has put into the fp16x3 window --
-        # convin, the Down / UpSamplers, the attention and its projections, a k x k output layer -- takes the per-sample max |x|
-        # its producer's epilogue left in a row of this arena (ha travels with h like the tile statistics hs), or a reduction
-        # over the tensor where the producer is not one of our epilogues (the network input).
-        h3 = self.conv_precision == "fp16x3"
-        # (the arena is zeroed by the input layer's own reduction launch when that is the first thing the forward does)
-        lazy = h3 and not isinstance(self.convin, _FourierInput) and not self.exact_input_layer
-        am = self._am = AmaxArena(ws, B, dev, zero=not lazy) if h3 else None
-
-        def slot(needed=True):
-            return am.row() if (h3 and needed) else None
-
-        def amax_of(t, ta):                                                      # the row that travels with t, else a reduction
-            if not h3:
-                return None
-            return ta if ta is not None else am.of(t)
-
         try:
-            H, W = x.shape[2:]
-            xe = None
-            if not cfg.bias:                                                         # punetg.py:390-394
-                ones = ws.take((B, 1, H, W), dev)
-                ones.fill_(1.0)
-                xe = ops.concat2(x, ones, out=ws.take((B, x.shape[1] + 1, H, W), dev))
-                ws.give(ones)
-                x = xe
-            ndown = len(self.downward_blocks)
-            bottom = list(self.before_block) + list(self.attn_resnet_block) + list(self.after_block)
-
-            def stats_for(nxt, C_, H_, W_):                                          # a statistics buffer only if the consumer reads it
-                return self._stats_buf(ws, B, C_, H_, W_, dev) if self._consumes_stats(nxt, C_, H_, W_) else None
-
-            def first_block_after_level(lv):
-                if lv + 1 < ndown and len(self.downward_blocks[lv + 1]):
-                    return self.downward_blocks[lv + 1][0]
-                return bottom[0] if bottom else None
-            if isinstance(self.convin, _FourierInput):
-                hs = None                                                            # no producer statistics: standalone first norm
-                h = ops.fourier_channels(x, self.convin.W, out=ws.take((B, cfg.model_channels, H, W), dev))
-            elif h3 and self.exact_input_layer:
-                # the input's channels are too far apart in magnitude for one exponent per sample (precision.escalate_input):
-                # exact-fp32 kernel, no tile statistics (the first block normalises standalone)
-                hs = None
-                # (circular= : a periodic network with exact_input_layer set by hand must raise -- the exact-fp32 kernel zero-pads)
-                h = ops.conv(x, pk[(id(self.convin), "exact")], bias=self.convin.bias, circular=self.circular,
-                             out=ws.take((B, cfg.model_channels, H, W), dev))
-            else:
-                first = self.downward_blocks[0][0] if (ndown and len(self.downward_blocks[0])) else (bottom[0] if bottom else None)
-                hs = stats_for(first, cfg.model_channels, H, W)
-                h = self._conv(self.convin, x, pk, tile_stats=hs, out=ws.take((B, cfg.model_channels, H, W), dev),
-                               in_amax=am.of_input(x, precision.input_layer_flag(self, dev), pk[(id(self.convin), "wmax")]) if h3 else None)
-            ha = None
-            if xe is not None:
-                ws.give(xe)
-            skips = []
-            for lv, blocks in enumerate(self.downward_blocks):                      # punetg.py:356-365
-                # pool_route: the DownSampler as a plain convolution of an already pooled tensor (a 3x3 fp16x3 packing only)
-                dpw = pk[id(self.downsamplers[lv].conv)]
-                plain_ds = (f == 2 and h3 and self.pool_route != "loader" and dpw.kind == "fp16x3" and dpw.ks == 3
-                            and dpw.subs is None)
-                pool = None
-                for j, blk in enumerate(blocks):
-                    ha2 = slot(j == len(blocks) - 1)                                 # the level's last block feeds the DownSampler
-                    nxt = blocks[j + 1] if j + 1 < len(blocks) else None             # ... and the skip: nobody normalises its result
-                    if j == len(blocks) - 1 and plain_ds and self.pool_route == "epilogue" and not (h.shape[2] % 2 or h.shape[3] % 2):
-                        pool = ops.PoolOut(ws.take((B, h.shape[1], h.shape[2] // 2, h.shape[3] // 2), dev))
-                    h2, hs2 = self._res(blk, h, sh(), pk, ws, xs=hs, out_amax=ha2, pool=pool,
-                                        want_stats=self._consumes_stats(nxt, h.shape[1], h.shape[2], h.shape[3]))
-                    give(h, hs)
-                    h, hs, ha = h2, hs2, ha2
-                skips.append(h)
-                if hs is not None:
-                    ws.give(hs)                                                      # the skip is only added, never normalised
-                ds = self.downsamplers[lv].conv
-                Ho, Wo = h.shape[2] // f, h.shape[3] // f
-                hs = stats_for(first_block_after_level(lv), ds.out_channels, Ho, Wo)
-                hp = None
-                if pool is not None:                                                 # "epilogue": the last block's store phase pooled
-                    if pool.written:
-                        hp = pool.tensor
-                    else:
-                        ws.give(pool.tensor)                                         # ... or its launch did not qualify: the loader
-                elif plain_ds and self.pool_route == "pass":
-                    hp = ops.maxpool_f(h, 2, out=ws.take((B, h.shape[1], Ho, Wo), dev))
-                if hp is not None:
-                    # max |maxpool(h)| <= max |h| (below); the persistent kernel takes the raw-input launch where the shape is its own
-                    h = self._conv(ds, hp, pk, tile_stats=hs, out=ws.take((B, ds.out_channels, Ho, Wo), dev),
-                                   in_amax=amax_of(h, ha), pc_raw=True)
-                    ws.give(hp)
-                elif f == 2:
-                    h = self._conv(ds, h, pk, load_mode=DS_LOAD_MAXPOOL2, tile_stats=hs,
-                                   out=ws.take((B, ds.out_channels, Ho, Wo), dev), in_amax=amax_of(h, ha))
-                else:
-                    # max |maxpool(h)| <= max |h|: the producer's row of the unpooled h stays a valid exponent bound
-                    hp = ops.maxpool_f(h, f, out=ws.take((B, h.shape[1], Ho, Wo), dev))
-                    h = self._conv(ds, hp, pk, tile_stats=hs, out=ws.take((B, ds.out_channels, Ho, Wo), dev),
-                                   in_amax=amax_of(h, ha))
-                    ws.give(hp)
-                ha = None
-            nattn, nafter = len(self.attn_resnet_block), len(self.after_block)
-            for j, blk in enumerate(self.before_block):                               # punetg.py:378-387
-                ha2 = slot(j == len(self.before_block) - 1 and nattn == 0 and nafter == 0 and ndown > 0)
-                nxt = bottom[j + 1] if (j + 1 < len(self.before_block) or nattn > 0) else None
-                h2, hs2 = self._res(blk, h, sh(), pk, ws, xs=hs, out_amax=ha2,
-                                    want_stats=self._consumes_stats(nxt, h.shape[1], h.shape[2], h.shape[3]))
-                give(h, hs)
-                h, hs, ha = h2, hs2, ha2
-            xa, xas, xaa = h, hs, ha
-            for i, blk in enumerate(self.attn_resnet_block):
-                last = i == nattn - 1
-                attn_next = i < len(self.attn_block)
-                # x + xa is folded into the last residual block's epilogue when no attention follows it
-                xaa2 = slot(attn_next or (last and nafter == 0 and ndown > 0))
-                # its result feeds the attention (no statistics read), the next block of this group, or -- the last -- after_block
-                nb = len(self.before_block)
-                nxt = None if attn_next else (bottom[nb + i + 1] if nb + i + 1 < len(bottom) else None)
-                xa2, xas2 = self._res(blk, xa, sh(), pk, ws, xs=xas,
-                                      res2=h if (last and not attn_next) else None, out_amax=xaa2,
-                                      want_stats=self._consumes_stats(nxt, xa.shape[1], xa.shape[2], xa.shape[3]))
-                if xa is not h:
-                    give(xa, xas)
-                xa, xas, xaa = xa2, xas2, xaa2
-                if attn_next:
-                    nxt = bottom[nb + i + 1] if nb + i + 1 < len(bottom) else None
-                    xas2 = stats_for(nxt, xa.shape[1], xa.shape[2], xa.shape[3])
-                    xaa2 = slot(last and nafter == 0 and ndown > 0)
-                    xa2 = self._attention(self.attn_block[i], xa, pk, ws, res2=h if last else None, tile_stats=xas2,
-                                          in_amax=amax_of(xa, xaa), out_amax=xaa2)
-                    give(xa, xas)
-                    xa, xas, xaa = xa2, xas2, xaa2
-            if nattn == 0:
-                xa, xas, xaa = ops.add(h, h, out=ws.take(h.shape, dev)), None, None
-            give(h, hs if xas is not hs else None)
-            h, hs, ha = xa, xas, xaa
-            for j, blk in enumerate(self.after_block):
-                ha2 = slot(j == nafter - 1 and ndown > 0)                            # feeds the first UpSampler
-                nxt = self.after_block[j + 1] if j + 1 < nafter else None
-                h2, hs2 = self._res(blk, h, sh(), pk, ws, xs=hs, out_amax=ha2,
-                                    want_stats=self._consumes_stats(nxt, h.shape[1], h.shape[2], h.shape[3]))
-                give(h, hs)
-                h, hs, ha = h2, hs2, ha2
-            nup = len(self.upward_blocks)
-            direct_out = self._out_is_direct(self.convout)
-            for lv, blocks in enumerate(self.upward_blocks):                         # punetg.py:367-376
-                us = self.upsamplers[lv].conv
-                skip = skips.pop()
-                hs2 = stats_for(blocks[0] if len(blocks) else None, skip.shape[1], skip.shape[2], skip.shape[3])
-                if f == 2:
-                    h2 = self._conv(us, h, pk, load_mode=DS_LOAD_UPSAMPLE2, res1=skip, tile_stats=hs2,
-                                    out=ws.take(skip.shape, dev), in_amax=amax_of(h, ha))
-                else:
-                    # a copy keeps max |h|: the producer's row bounds the upsampled tensor too
-                    hu = ops.upsample_f(h, f, out=ws.take((B, h.shape[1]) + tuple(skip.shape[2:]), dev))
-                    h2 = self._conv(us, hu, pk, res1=skip, tile_stats=hs2, out=ws.take(skip.shape, dev), in_amax=amax_of(h, ha))
-                    ws.give(hu)
-                give(h, hs)
-                ws.give(skip)
-                h, hs, ha = h2, hs2, None
-                for j, blk in enumerate(blocks):
-                    lastb = j == len(blocks) - 1
-                    final = lv == nup - 1 and lastb                                  # feeds convout: no norm follows
-                    ha2 = slot(lastb and (not final or not direct_out))              # the next UpSampler, or a matrix-core output layer
-                    nxt = None if lastb else blocks[j + 1]                           # the last one feeds an UpSampler or convout: no norm follows
-                    h2, hs2 = self._res(blk, h, sh(), pk, ws, xs=hs, out_amax=ha2,
-                                        want_stats=self._consumes_stats(nxt, h.shape[1], h.shape[2], h.shape[3]))
-                    give(h, hs)
-                    h, hs, ha = h2, hs2, ha2
-            y = self._out_conv(self.convout, h, pk, out, self.circular, in_amax=None if direct_out else amax_of(h, ha))
-            give(h, hs)
-            return y
+            d = (_Volumes if self.dim == 3 else _Fields)(self, x, shifts, row)
+            return self._walk(d, x.contiguous() if self.dim == 3 else x, out)
         finally:
-            if am is not None:
-                am.release()
-            self._am = None
-            if lazy_shifts is not None:
-                lazy_shifts.release()
+            if self._am is not None:                       # the arena a field pass set for its launches
+                self._am.release()
+                self._am = None
+            if isinstance(shifts, _FieldShifts):
+                shifts.release()
 
-    # ------------------------------------------------------------------ volumes (dimension = 3)
-    def _forward3d(self, x, shifts, row=None, out=None):
-        """The same network on [B, C, D, H, W] volumes (punetg.py:217-236,389-416 with Conv3d / MaxPool3d /
-        Upsample / ThreeDimensionalAttention).  Convolutions: with the default fp16x3 precision three launches of the 2-D
-        matrix-core kernels per 3x3x3 convolution over a slice-major copy of the volume (ops.conv3d_mfma); otherwise, and
-        for the <= 4-channel output layer, the exact-fp32 direct kernel (ops.conv3d) -- both with the pooling /
-        upsampling / skip / residual / time-shift fusions of the 2-D path.  Standalone per-(sample, channel) norms over
-        D*H*W, attention over the flattened voxels.  All buffers come from the workspace: the sampler's planner captures
-        this path as a hipGraph too."""
-        if x.dim() != 5:
-            raise ValueError("a dimension=3 network takes [B, C, D, H, W] volumes")
-        pk = self.packed_weights()
-        ws = self._ws
-        cfg = self.config
-        B, dev = x.shape[0], x.device
-        # a field of time shifts (_FieldShifts): every block evaluates its own per-voxel shift and adds it as conv1's residual
-        lazy_shifts = shifts if isinstance(shifts, _FieldShifts) else None
-        it = iter(range(len(shifts))) if lazy_shifts is None else None
-        k1, k2 = self.norm_kinds
+    def _walk(self, d, x, out):
+        """The network once (punetg.py:356-416): levels, skip stack, bottom group with x + xa folded into the attention group's
+        last launch, output layer.  An activation is a record (tensor, the statistics its producer left or None, the amax row
+        its producer filled or None), and every producer is told who consumes its result (`to`): the residual block that will
+        normalise it, the module of the raw-input launch that reads it as it is (Down / UpSampler, attention, output layer), or
+        None for anything else.  Whether that earns statistics or a row is the dimension's business.  Every buffer comes from
+        the workspace -- the sampler's planner captures this as a hipGraph -- and goes back as soon as its reader has run."""
+        ws, cfg = self._ws, self.config
+        B, dev, sides = x.shape[0], x.device, tuple(x.shape[2:])
 
-        def sh():
-            return shift_rows(shifts[next(it)], row, B)
+        def give(a):
+            ws.give(a[0])
+            if a[1] is not None:
+                ws.give(a[1])
 
-        # Norm folding on volumes (round 2; fp16x3, 3x3x3 kernels; round 3: periodic padding too): every activation travels with the partial
-        # sums its producer's slice -> volume copy left (hs); a block whose input has them runs ops.resblock3d_fused --
-        # norm1 inside the volume -> slice copy, the intermediate slice-major with norm2 in conv2's loader -- 20 instead of
-        # 52 bytes per element of norm / copy traffic per block.  Without statistics (after the thin input layer or the
-        # attention) the block runs the standalone norms and leaves statistics for its successor.
-        # (not with a field of shifts: resblock3d_fused adds one shift per channel, so those blocks run the standalone norms)
-        fold = (self._fused() and self.extra_residual is None and k1 != 3 and k2 != 3 and cfg.kernel_size == 3
-                and lazy_shifts is None)
+        def chain(blocks, a, to):
+            """a through residual blocks, each input given back once its block has run; `to` consumes the last result."""
+            for j, blk in enumerate(blocks):
+                a2 = d.res(blk, a, blocks[j + 1] if j + 1 < len(blocks) else to)
+                give(a)
+                a = a2
+            return a
 
-        def stats_buf(shape):
-            Bc, C, D, H, W = shape
-            return ws.take((Bc, C, ops.volume_stat_tiles(D, H * W), 4), dev)
-
-        def conv(m, h, load_mode=0, dst=None, fresh=False, want_stats=False, normalised=False, **kw):
-            """-> (tensor, statistics or None).  Every buffer comes from the workspace (a captured loop must not allocate);
-            fresh: the caller's result.  normalised: h is a norm + SiLU output inside the fp16x3 window; otherwise the
-            matrix-core route measures per-slice activation exponents on its slice copy (ops.conv3d_mfma)."""
-            f = {0: (1, 1), DS_LOAD_MAXPOOL2: (1, 2), DS_LOAD_UPSAMPLE2: (2, 1)}[load_mode]
-            shape = (h.shape[0], m.out_channels) + tuple(v * f[0] // f[1] for v in h.shape[2:])
-            if dst is None and not fresh:
-                dst = ws.take(shape, dev)
-            packs = pk.get((id(m), "3d"))
-            # fp16x3 (default): three 2-D MFMA launches per convolution -- 0.30 vs 1.33 ms at 64 -> 64 channels, 8 x 32^3;
-            # the thin input / output layers stay on the direct kernel (0.08 vs 0.14 ms for 1 -> 64)
-            k = m.weight.shape[-1]
-            if packs is None and k != 3:
-                raise NotImplementedError(f"{k}x{k}x{k} kernels on volumes are implemented on the fp16x3 convolution only "
-                                          f"(conv_precision={self.conv_precision!r})")
-            if packs is not None and ((m.out_channels > 4 and m.in_channels > 4) or k != 3):
-                st = stats_buf(shape) if (fold and want_stats) else None
-                return ops.conv3d_mfma(h, packs, bias=m.bias, circular=self.circular, load_mode=load_mode, out=dst, ws=ws,
-                                       out_stats=st, in_amax=ops.NORMALISED if normalised else None, **kw), st
-            return ops.conv3d(h, pk.get((id(m), "eff"), m.weight), bias=m.bias, circular=self.circular, load_mode=load_mode,
-                              out=dst, **kw), None
-
-        def give(t, ts=None):
-            ws.give(t)
-            if ts is not None:
-                ws.give(ts)
-
-        def res(blk, h, hs, res2=None, want_stats=True):                          # ResnetBlockC.forward; h untouched
-            w1, b1 = getattr(blk.gnorm1, "weight", None), getattr(blk.gnorm1, "bias", None)
-            w2, b2 = getattr(blk.gnorm2, "weight", None), getattr(blk.gnorm2, "bias", None)
-            C = h.shape[1]
-            p1, p2 = pk.get((id(blk.conv1), "3d")), pk.get((id(blk.conv2), "3d"))
-            windowed = k1 in (0, 1) and k2 in (0, 1) and self._norms_in_window(blk)
-            if (fold and windowed and hs is not None and p1 is not None and p2 is not None and C > 4
-                    and (C + 63) // 64 <= self.fuse_max_cot):
-                tab = ops.inorm_table(hs, w1, b1, k1, h[0, 0].numel(), eps=1e-5, out=ws.take((B, ops.table_channels(C), 4), dev))
-                os_ = stats_buf(h.shape) if want_stats else None
-                y = ops.resblock3d_fused(h, tab, p1, blk.conv1.bias, sh(), p2, blk.conv2.bias, w2, b2, k2, res2=res2,
-                                         out=ws.take(h.shape, dev), out_stats=os_, ws=ws, circular=self.circular)
-                ws.give(tab)
-                return y, os_
-            a = ops.inorm_silu(h, w1, b1, kind=k1, eps=1e-5, out=ws.take(h.shape, dev))
-            if lazy_shifts is not None:
-                yt = self._field_shift(blk, lazy_shifts, *h.shape[2:])
-                y, _ = conv(blk.conv1, a, res1=yt.view((B, blk.conv1.out_channels) + tuple(h.shape[2:])), normalised=windowed)
-                ws.give(yt)
-            else:
-                y, _ = conv(blk.conv1, a, shift=sh(), normalised=windowed)
-            ops.inorm_silu(y, w2, b2, kind=k2, eps=1e-5, out=a)
-            if self.extra_residual is None:
-                _, os_ = conv(blk.conv2, a, res1=h, res2=res2, dst=y, want_stats=want_stats, normalised=windowed)
-            else:
-                conv(blk.conv2, a, res1=h, dst=y, normalised=windowed)
-                ops.add(y, self.extra_residual(h).contiguous(), out=y)
-                if res2 is not None:
-                    ops.add(y, res2, out=y)
-                os_ = None
-            ws.give(a)
-            return y, os_
-
-        def attn(att, h, res2=None):                                              # ThreeDimensionalAttention
-            Bq, E, D, H, W = h.shape
-            r2 = None if res2 is None else res2.view(Bq, E, D * H, W)
-            y = self._attention(att, h.view(Bq, E, D * H, W), pk, ws, res2=r2)
-            o = ws.take(h.shape, dev)
-            o.copy_(y.view(h.shape))
-            ws.give(y)
-            return o
-
-        x = x.contiguous()
         xe = None
-        if not cfg.bias:                                                          # punetg.py:390-394
-            ones = ws.take((B, 1) + tuple(x.shape[2:]), dev)
+        if not cfg.bias:                                                             # punetg.py:390-394
+            ones = ws.take((B, 1) + sides, dev)
             ones.fill_(1.0)
-            xe = ops.concat2(x, ones, out=ws.take((B, x.shape[1] + 1) + tuple(x.shape[2:]), dev))
+            xe = ops.concat2(x, ones, out=ws.take((B, x.shape[1] + 1) + sides, dev))
             ws.give(ones)
             x = xe
-        hs = None
-        if isinstance(self.convin, _FourierInput):
-            h = ops.fourier_channels(x, self.convin.W, out=ws.take((B, cfg.model_channels) + tuple(x.shape[2:]), dev))
+        ndown, nup = len(self.downward_blocks), len(self.upward_blocks)
+        bottom = list(self.before_block) + list(self.attn_resnet_block) + list(self.after_block)
+        # who reads the bottom's result raw: the first UpSampler.  (A network without levels hands it to the output layer, which
+        # reduces its input itself: None.)
+        rest = self.upsamplers[0] if ndown else None
+
+        def entering(lv):                                                            # the block that normalises what enters level lv
+            if lv < ndown and len(self.downward_blocks[lv]):
+                return self.downward_blocks[lv][0]
+            return bottom[0] if bottom else None
+        if isinstance(self.convin, _FourierInput):                                   # no producer statistics: standalone first norm
+            a = ops.fourier_channels(x, self.convin.W, out=ws.take((B, cfg.model_channels) + sides, dev)), None, None
         else:
-            h, hs = conv(self.convin, x, want_stats=True)
+            a = d.conv_in(x, entering(0))
         if xe is not None:
             ws.give(xe)
         skips = []
-        for lv, blocks in enumerate(self.downward_blocks):
-            for blk in blocks:
-                h2, hs2 = res(blk, h, hs)
-                give(h, hs)
-                h, hs = h2, hs2
-            skips.append(h)
-            if hs is not None:
-                ws.give(hs)                                                      # the skip is only added, never normalised
-            if self.factor == 2:
-                h, hs = conv(self.downsamplers[lv].conv, h, load_mode=DS_LOAD_MAXPOOL2, want_stats=True)
-            else:                                                                # pooled volume, then the plain convolution
-                pooled = tuple(h.shape[:2]) + tuple(v // self.factor for v in h.shape[2:])
-                hp = ops.maxpool_f(h, self.factor, out=ws.take(pooled, dev))
-                h, hs = conv(self.downsamplers[lv].conv, hp, want_stats=True)
-                ws.give(hp)
-        for blk in self.before_block:
-            h2, hs2 = res(blk, h, hs)
-            give(h, hs)
-            h, hs = h2, hs2
-        xa, xas = h, hs
-        nattn = len(self.attn_resnet_block)
+        for lv, blocks in enumerate(self.downward_blocks):                          # punetg.py:356-365
+            a = chain(blocks, a, self.downsamplers[lv])
+            skips.append(a[0])
+            if a[1] is not None:
+                ws.give(a[1])                                                        # the skip is only added, never normalised
+            a = d.down(self.downsamplers[lv], a, entering(lv + 1))
+        nbefore, nattn, nafter = len(self.before_block), len(self.attn_resnet_block), len(self.after_block)
+        # punetg.py:378-387.  Without an attention group x + x follows, which reads no statistics (and, between blocks, no row)
+        a = chain(self.before_block, a, self.attn_resnet_block[0] if nattn else (None if nafter else rest))
+        xa = a
         for i, blk in enumerate(self.attn_resnet_block):
             last = i == nattn - 1
-            xa2, xas2 = res(blk, xa, xas, res2=h if (last and i >= len(self.attn_block)) else None)
-            if xa is not h:
-                give(xa, xas)
-            xa, xas = xa2, xas2
-            if i < len(self.attn_block):
-                xa2 = attn(self.attn_block[i], xa, res2=h if last else None)
-                give(xa, xas)
-                xa, xas = xa2, None
+            att = self.attn_block[i] if i < len(self.attn_block) else None
+            after = bottom[nbefore + i + 1] if nbefore + i + 1 < len(bottom) else rest
+            # x + xa is folded into the last residual block's epilogue when no attention follows it
+            xa2 = d.res(blk, xa, after if att is None else att, res2=a[0] if (last and att is None) else None)
+            if xa is not a:
+                give(xa)
+            xa = xa2
+            if att is not None:
+                xa2 = d.attn(att, xa, after, res2=a[0] if last else None)
+                give(xa)
+                xa = xa2
         if nattn == 0:
-            xa, xas = ops.add(h, h, out=ws.take(h.shape, dev)), None
-        give(h, hs if xas is not hs else None)
-        h, hs = xa, xas
-        for blk in self.after_block:
-            h2, hs2 = res(blk, h, hs)
-            give(h, hs)
-            h, hs = h2, hs2
-        nup = len(self.upward_blocks)
-        for lv, blocks in enumerate(self.upward_blocks):
+            xa = ops.add(a[0], a[0], out=ws.take(a[0].shape, dev)), None, None
+        give(a)
+        a = chain(self.after_block, xa, rest)
+        for lv, blocks in enumerate(self.upward_blocks):                             # punetg.py:367-376
             skip = skips.pop()
-            if self.factor == 2:
-                h2, hs2 = conv(self.upsamplers[lv].conv, h, load_mode=DS_LOAD_UPSAMPLE2, res1=skip, want_stats=True)
-            else:
-                hu = ops.upsample_f(h, self.factor, out=ws.take(tuple(h.shape[:2]) + tuple(skip.shape[2:]), dev))
-                h2, hs2 = conv(self.upsamplers[lv].conv, hu, res1=skip, want_stats=True)
-                ws.give(hu)
-            give(h, hs)
+            a2 = d.up(self.upsamplers[lv], a, skip, blocks[0] if len(blocks) else None)
+            give(a)
             ws.give(skip)
-            h, hs = h2, hs2
-            for j, blk in enumerate(blocks):
-                final = lv == nup - 1 and j == len(blocks) - 1                    # feeds convout: no norm follows
-                h2, hs2 = res(blk, h, hs, want_stats=not final)
-                give(h, hs)
-                h, hs = h2, hs2
-        y, _ = conv(self.convout, h, dst=out, fresh=out is None)
-        give(h, hs)
+            a = chain(blocks, a2, self.upsamplers[lv + 1] if lv + 1 < nup else self.convout)
+        y = d.out(a, out)
+        give(a)
         return y
 
     def _attention(self, att, x, pk, ws, res2=None, tile_stats=None, in_amax=None, out_amax=None):
@@ -1376,6 +1067,251 @@ class PUNetG(torch.nn.Module):
         if own is not None:
             own.release()
         return y
+
+
+def _shift_source(shifts, row, B):
+    """-> sh(), the next residual block's time shift: tabulated shifts in block order, row `row` of each (runtime.shift_rows);
+    a field of shifts goes to every block as it is, and the block evaluates its own (PUNetG._field_shift)."""
+    if isinstance(shifts, _FieldShifts):
+        return lambda: shifts
+    it = iter(shifts)
+    return lambda: shift_rows(next(it), row, B)
+
+
+class _Fields:
+    """What PUNetG._walk launches on [B, C, H, W] fields.  Every activation travels with the tile statistics its producer left --
+    asked for only where the consuming block reads them (`_consumes_stats`) -- and, where it feeds a raw-input launch, with an
+    amax row.  Activation exponents (ops.py): every launch that reads a tensor which no norm has put into the fp16x3 window --
+    convin, the Down / UpSamplers, the attention and its projections, a k x k output layer -- takes the per-sample max |x| its
+    producer's epilogue left in a row of the pass's arena, or a reduction over the tensor where the producer is not one of our
+    epilogues (the network input) or left none."""
+
+    def __init__(self, net, x, shifts, row):
+        if net.pool_route not in POOL_ROUTES:
+            raise ValueError(f"pool_route {net.pool_route!r}; choose from {POOL_ROUTES}")
+        self.net, self.pk, self.ws = net, net.packed_weights(), net._ws
+        self.B, self.dev = x.shape[0], x.device
+        self.sh = _shift_source(shifts, row, self.B)       # a field handed over as a tensor allocates: not for captured runs
+        self.h3 = net.conv_precision == "fp16x3"
+        # (the arena is zeroed by the input layer's own reduction launch when that is the first thing the forward does)
+        lazy = self.h3 and not isinstance(net.convin, _FourierInput) and not net.exact_input_layer
+        self.am = net._am = AmaxArena(self.ws, self.B, self.dev, zero=not lazy) if self.h3 else None
+        self.direct_out = net._out_is_direct(net.convout)
+        self.pool = None                                    # "epilogue": the PoolOut a level's last block may have filled
+
+    def stats(self, to, C, H, W):
+        """A statistics buffer for a [B, C, H, W] result, only if its consumer reads it."""
+        if not self.net._consumes_stats(to if isinstance(to, _ResBlock) else None, C, H, W):
+            return None
+        return self.net._stats_buf(self.ws, self.B, C, H, W, self.dev)
+
+    def row(self, to):
+        """A zeroed amax row for a result that feeds a raw-input launch (the direct output layer computes in fp32: none)."""
+        raw = to is not None and not isinstance(to, _ResBlock) and not (to is self.net.convout and self.direct_out)
+        return self.am.row() if (self.h3 and raw) else None
+
+    def amax_of(self, a):
+        """The row that travels with a, else a reduction."""
+        if not self.h3:
+            return None
+        return a[2] if a[2] is not None else self.am.of(a[0])
+
+    def plain_down(self, smp):
+        """pool_route: this DownSampler as a plain convolution of an already pooled tensor (a 3x3 fp16x3 packing only)."""
+        pw = self.pk[id(smp.conv)]
+        return (self.net.factor == 2 and self.h3 and self.net.pool_route != "loader" and pw.kind == "fp16x3" and pw.ks == 3
+                and pw.subs is None)
+
+    def conv_in(self, x, to):
+        net, m = self.net, self.net.convin
+        shape = (self.B, m.out_channels) + tuple(x.shape[2:])
+        if self.h3 and net.exact_input_layer:
+            # the input's channels are too far apart in magnitude for one exponent per sample (precision.escalate_input):
+            # exact-fp32 kernel, no tile statistics (the first block normalises standalone)
+            # (circular= : a periodic network with exact_input_layer set by hand must raise -- the exact-fp32 kernel zero-pads)
+            return ops.conv(x, self.pk[(id(m), "exact")], bias=m.bias, circular=net.circular, out=self.ws.take(shape, self.dev)), None, None
+        hs = self.stats(to, *shape[1:])
+        wmax = self.pk.get((id(m), "wmax"))
+        return net._conv(m, x, self.pk, tile_stats=hs, out=self.ws.take(shape, self.dev),
+                         in_amax=self.am.of_input(x, precision.input_layer_flag(net, self.dev), wmax) if self.h3 else None), hs, None
+
+    def res(self, blk, a, to, res2=None):
+        net, (h, hs, _) = self.net, a
+        ha = self.row(to)
+        if (any(to is s for s in net.downsamplers) and self.plain_down(to) and net.pool_route == "epilogue"
+                and not (h.shape[2] % 2 or h.shape[3] % 2)):
+            self.pool = ops.PoolOut(self.ws.take((self.B, h.shape[1], h.shape[2] // 2, h.shape[3] // 2), self.dev))
+        h2, hs2 = net._res(blk, h, self.sh(), self.pk, self.ws, res2=res2, xs=hs, out_amax=ha, pool=self.pool,
+                           want_stats=net._consumes_stats(to if isinstance(to, _ResBlock) else None, *h.shape[1:]))
+        return h2, hs2, ha
+
+    def down(self, smp, a, to):
+        """DownSampler (max-pool -> conv) of the level's last result, which stays with the caller as the skip."""
+        net, ws, f, h, ds = self.net, self.ws, self.net.factor, a[0], smp.conv
+        Ho, Wo = h.shape[2] // f, h.shape[3] // f
+        hs = self.stats(to, ds.out_channels, Ho, Wo)
+        pool, self.pool = self.pool, None
+        hp = None
+        if pool is not None and pool.written:                                    # "epilogue": the last block's store phase pooled
+            hp = pool.tensor
+        elif pool is not None:
+            ws.give(pool.tensor)                                                 # ... or its launch did not qualify: the loader
+        plain = hp is not None or (self.plain_down(smp) and net.pool_route == "pass")
+        if hp is None and (plain or f != 2):
+            hp = ops.maxpool_f(h, f, out=ws.take((self.B, h.shape[1], Ho, Wo), self.dev))
+        # max |maxpool(h)| <= max |h|: the producer's row of the unpooled h stays a valid exponent bound.  plain: the persistent
+        # kernel takes the raw-input launch where the shape is its own; factor 2 otherwise: the convolution's loader pools
+        kw = {"load_mode": DS_LOAD_MAXPOOL2} if hp is None else ({"pc_raw": True} if plain else {})
+        y = net._conv(ds, h if hp is None else hp, self.pk, tile_stats=hs, out=ws.take((self.B, ds.out_channels, Ho, Wo), self.dev),
+                      in_amax=self.amax_of(a), **kw)
+        if hp is not None:
+            ws.give(hp)
+        return y, hs, None
+
+    def up(self, smp, a, skip, to):
+        """UpSampler (nearest -> conv) + skip; factor 2 upsamples in the convolution's loader."""
+        net, ws, f, h = self.net, self.ws, self.net.factor, a[0]
+        hs = self.stats(to, *skip.shape[1:])
+        # a copy keeps max |h|: the producer's row bounds the upsampled tensor too
+        hu = None if f == 2 else ops.upsample_f(h, f, out=ws.take((self.B, h.shape[1]) + tuple(skip.shape[2:]), self.dev))
+        y = net._conv(smp.conv, h if hu is None else hu, self.pk, res1=skip, tile_stats=hs, out=ws.take(skip.shape, self.dev),
+                      in_amax=self.amax_of(a), **({"load_mode": DS_LOAD_UPSAMPLE2} if hu is None else {}))
+        if hu is not None:
+            ws.give(hu)
+        return y, hs, None
+
+    def attn(self, att, a, to, res2=None):
+        hs, ha = self.stats(to, *a[0].shape[1:]), self.row(to)
+        return self.net._attention(att, a[0], self.pk, self.ws, res2=res2, tile_stats=hs, in_amax=self.amax_of(a), out_amax=ha), hs, ha
+
+    def out(self, a, out):
+        net = self.net
+        return net._out_conv(net.convout, a[0], self.pk, out, net.circular, in_amax=None if self.direct_out else self.amax_of(a))
+
+
+class _Volumes:
+    """What PUNetG._walk launches on [B, C, D, H, W] volumes (punetg.py:217-236,389-416 with Conv3d / MaxPool3d / Upsample /
+    ThreeDimensionalAttention).  Convolutions: with the default fp16x3 precision three launches of the 2-D matrix-core kernels per
+    3x3x3 convolution over a slice-major copy of the volume (ops.conv3d_mfma, which measures activation exponents per slice: no
+    amax rows here); otherwise, and for the <= 4-channel output layer, the exact-fp32 direct kernel (ops.conv3d) -- both with the
+    pooling / upsampling / skip / residual / time-shift fusions of the 2-D path.  Per-(sample, channel) norms over D*H*W, attention
+    over the flattened voxels.
+
+    Norm folding (fp16x3, 3x3x3 kernels, zero or periodic padding): every activation travels with the partial sums its producer's
+    slice -> volume copy left; a block whose input has them runs ops.resblock3d_fused -- norm1 inside the volume -> slice copy,
+    the intermediate slice-major with norm2 in conv2's loader -- 20 instead of 52 bytes per element of norm / copy traffic per
+    block.  Without statistics (after the thin input layer or the attention) the block runs the standalone norms and leaves
+    statistics for its successor.  Every producer but the one before the output layer leaves them.  Not with a field of shifts:
+    resblock3d_fused adds one shift per channel, so those blocks run the standalone norms."""
+
+    def __init__(self, net, x, shifts, row):
+        if x.dim() != 5:
+            raise ValueError("a dimension=3 network takes [B, C, D, H, W] volumes")
+        self.net, self.pk, self.ws = net, net.packed_weights(), net._ws
+        self.B, self.dev = x.shape[0], x.device
+        self.sh = _shift_source(shifts, row, self.B)
+        self.field = shifts if isinstance(shifts, _FieldShifts) else None
+        k1, k2 = net.norm_kinds
+        self.fold = (net._fused() and net.extra_residual is None and k1 != 3 and k2 != 3 and net.config.kernel_size == 3
+                     and self.field is None)
+
+    def stats_buf(self, shape):
+        Bc, C, D, H, W = shape
+        return self.ws.take((Bc, C, ops.volume_stat_tiles(D, H * W), 4), self.dev)
+
+    def conv(self, m, h, load_mode=0, dst=None, fresh=False, want_stats=False, normalised=False, **kw):
+        """-> an activation.  Every buffer comes from the workspace (a captured loop must not allocate); fresh: the caller's
+        result.  normalised: h is a norm + SiLU output inside the fp16x3 window; otherwise the matrix-core route measures
+        per-slice activation exponents on its slice copy (ops.conv3d_mfma)."""
+        net, pk = self.net, self.pk
+        f = {0: (1, 1), DS_LOAD_MAXPOOL2: (1, 2), DS_LOAD_UPSAMPLE2: (2, 1)}[load_mode]
+        shape = (h.shape[0], m.out_channels) + tuple(v * f[0] // f[1] for v in h.shape[2:])
+        if dst is None and not fresh:
+            dst = self.ws.take(shape, self.dev)
+        packs = pk.get((id(m), "3d"))
+        # fp16x3 (default): three 2-D MFMA launches per convolution -- 0.30 vs 1.33 ms at 64 -> 64 channels, 8 x 32^3;
+        # the thin input / output layers stay on the direct kernel (0.08 vs 0.14 ms for 1 -> 64)
+        k = m.weight.shape[-1]
+        if packs is None and k != 3:
+            raise NotImplementedError(f"{k}x{k}x{k} kernels on volumes are implemented on the fp16x3 convolution only "
+                                      f"(conv_precision={net.conv_precision!r})")
+        if packs is not None and ((m.out_channels > 4 and m.in_channels > 4) or k != 3):
+            st = self.stats_buf(shape) if (self.fold and want_stats) else None
+            return ops.conv3d_mfma(h, packs, bias=m.bias, circular=net.circular, load_mode=load_mode, out=dst, ws=self.ws,
+                                   out_stats=st, in_amax=ops.NORMALISED if normalised else None, **kw), st, None
+        return ops.conv3d(h, pk.get((id(m), "eff"), m.weight), bias=m.bias, circular=net.circular, load_mode=load_mode,
+                          out=dst, **kw), None, None
+
+    def conv_in(self, x, to):
+        return self.conv(self.net.convin, x, want_stats=True)
+
+    def res(self, blk, a, to, res2=None):                                         # ResnetBlockC.forward; the input untouched
+        net, pk, ws, B, dev = self.net, self.pk, self.ws, self.B, self.dev
+        h, hs, _ = a
+        want_stats = to is not net.convout                                        # no norm follows
+        k1, k2 = net.norm_kinds
+        w1, b1 = getattr(blk.gnorm1, "weight", None), getattr(blk.gnorm1, "bias", None)
+        w2, b2 = getattr(blk.gnorm2, "weight", None), getattr(blk.gnorm2, "bias", None)
+        C = h.shape[1]
+        p1, p2 = pk.get((id(blk.conv1), "3d")), pk.get((id(blk.conv2), "3d"))
+        windowed = k1 in (0, 1) and k2 in (0, 1) and net._norms_in_window(blk)
+        if (self.fold and windowed and hs is not None and p1 is not None and p2 is not None and C > 4
+                and (C + 63) // 64 <= net.fuse_max_cot):
+            tab = ops.inorm_table(hs, w1, b1, k1, h[0, 0].numel(), eps=1e-5, out=ws.take((B, ops.table_channels(C), 4), dev))
+            os_ = self.stats_buf(h.shape) if want_stats else None
+            y = ops.resblock3d_fused(h, tab, p1, blk.conv1.bias, self.sh(), p2, blk.conv2.bias, w2, b2, k2, res2=res2,
+                                     out=ws.take(h.shape, dev), out_stats=os_, ws=ws, circular=net.circular)
+            ws.give(tab)
+            return y, os_, None
+        act = ops.inorm_silu(h, w1, b1, kind=k1, eps=1e-5, out=ws.take(h.shape, dev))
+        if self.field is not None:     # every block evaluates its own per-voxel shift and adds it as conv1's residual
+            yt = net._field_shift(blk, self.field, *h.shape[2:])
+            y = self.conv(blk.conv1, act, res1=yt.view((B, blk.conv1.out_channels) + tuple(h.shape[2:])), normalised=windowed)[0]
+            ws.give(yt)
+        else:
+            y = self.conv(blk.conv1, act, shift=self.sh(), normalised=windowed)[0]
+        ops.inorm_silu(y, w2, b2, kind=k2, eps=1e-5, out=act)
+        if net.extra_residual is None:
+            os_ = self.conv(blk.conv2, act, res1=h, res2=res2, dst=y, want_stats=want_stats, normalised=windowed)[1]
+        else:
+            self.conv(blk.conv2, act, res1=h, dst=y, normalised=windowed)
+            ops.add(y, net.extra_residual(h).contiguous(), out=y)
+            if res2 is not None:
+                ops.add(y, res2, out=y)
+            os_ = None
+        ws.give(act)
+        return y, os_, None
+
+    def down(self, smp, a, to):
+        h, f = a[0], self.net.factor
+        if f == 2:
+            return self.conv(smp.conv, h, load_mode=DS_LOAD_MAXPOOL2, want_stats=True)
+        hp = ops.maxpool_f(h, f, out=self.ws.take(tuple(h.shape[:2]) + tuple(v // f for v in h.shape[2:]), self.dev))
+        y = self.conv(smp.conv, hp, want_stats=True)                              # pooled volume, then the plain convolution
+        self.ws.give(hp)
+        return y
+
+    def up(self, smp, a, skip, to):
+        h, f = a[0], self.net.factor
+        if f == 2:
+            return self.conv(smp.conv, h, load_mode=DS_LOAD_UPSAMPLE2, res1=skip, want_stats=True)
+        hu = ops.upsample_f(h, f, out=self.ws.take(tuple(h.shape[:2]) + tuple(skip.shape[2:]), self.dev))
+        y = self.conv(smp.conv, hu, res1=skip, want_stats=True)
+        self.ws.give(hu)
+        return y
+
+    def attn(self, att, a, to, res2=None):                                        # ThreeDimensionalAttention
+        h = a[0]
+        Bq, E, D, H, W = h.shape
+        r2 = None if res2 is None else res2.view(Bq, E, D * H, W)
+        y = self.net._attention(att, h.view(Bq, E, D * H, W), self.pk, self.ws, res2=r2)
+        o = self.ws.take(h.shape, self.dev)
+        o.copy_(y.view(h.shape))
+        self.ws.give(y)
+        return o, None, None
+
+    def out(self, a, out):
+        return self.conv(self.net.convout, a[0], dst=out, fresh=out is None)[0]
 
 
 class PUNetGCond(PUNetG):

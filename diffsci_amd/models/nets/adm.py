@@ -3,17 +3,28 @@
 Same constructor, ``net(x, t, y=None)`` protocol and state_dict key names as the reference's
 ``ADM`` / ``ADMConfig`` (adm.py:8-216), for the default family: 2-D fields, default convolutions,
 GroupLN(1 group) + GroupRMS(1 group) norms, avg-pool down / nearest up by transition_scale_factor inside the
-last block of a layer, decoder_type 1 or 2, single-head attention in the middle block.  The torch.nn layers are
-parameter containers only; every tensor operation is a launch into libdiffsci_hip.so:
+last block of a layer, decoder_type 1 or 2, attention with `attn_heads` heads in the middle block.  The torch.nn layers are
+parameter containers only; every tensor operation is a launch into libdiffsci_hip.so (the entry points the host launch trace of
+tests/net_trace.py lists, tests/golden/adm_trace.json.gz):
 
-  input/output layer, conv1 (+nearest-up load), conv2 (+residual)   ds_conv2d*
-  convresidual (1x1, +nearest-up load)                              ds_conv2d
-  GroupNorm(1,C)+SiLU [+AvgPool2d], GroupRMSNorm(1,C)+FiLM+SiLU      ds_gnorm1_stats, ds_gnorm1_apply
-  AvgPool2d on the residual branch                                  ds_gnorm1_apply (kind 2)
-  resampling by a factor other than 2                               ds_gnorm1_apply_poolf, ds_upsample_f
-  skip concat / add                                                 ds_concat2 / ds_add
-  ADMTimeEmbedding, embed_linear                                    ds_fourier_features, ds_linear, ds_add_act
-  attention                                                         ds_conv2d (1x1) + ds_attention*
+  input layer                           ds_input_amax | ds_absmax_rows, then the 3x3 convolution; exact_input_layer: ds_conv2d
+  conv1, conv2 (+ residual), a wide     ds_conv2d_h3 -- the norm folded into its loader by ds_gnorm1_table, narrow layers --,
+    output layer (3x3)                    ds_conv2d_h3_img (a standalone norm's images); after nearest x2: ds_conv2d_h3 with the
+                                          upsampling loader, or the parity kernels ds_conv2d_h3_up / ds_conv2d_h3_up_img;
+                                          conv_precision "bf16x6" / "fp32": ds_conv2d_x6 / ds_conv2d
+  output layer of up to 4 channels      ds_conv2d_direct
+  convresidual, attention in / out      ds_conv1x1_h3 (AvgPool2d(2) / nearest x2 in its loader, x2 residual in conv2's epilogue),
+    projections (1x1)                     ds_conv2d
+  standalone GroupNorm(1,C) /           ds_gnorm1_stats_tiles (the producer's tile statistics) | ds_gnorm1_stats (a pass), then
+    GroupRMSNorm(1,C) [+FiLM] + SiLU      ds_gnorm1_apply [+ AvgPool2d(2)] | ds_gnorm1_apply_images
+  AvgPool2d(2) on the residual branch   the 1x1 loader, or ds_gnorm1_apply (kind 2)
+  resampling by a factor other than 2   ds_gnorm1_apply_poolf, ds_upsample_f
+  skip concat / add                     ds_concat2 + ds_amax_merge / ds_add + ds_absmax_rows
+  amax rows (activation exponents)      ds_input_amax, ds_fill_u32, ds_absmax_rows, ds_amax_merge, the convolutions' epilogues
+  ADMTimeEmbedding, embed_linear        ds_fourier_features, ds_linear, ds_add_act
+  attention core                        ds_attention_h3, ds_attention_generic, ds_attention_heads_generic
+  stand-alone blocks on volumes         ds_volume_to_slices, ds_conv2d_h3 x 3, ds_slices_to_volume | ds_conv3d_direct;
+                                          ds_avgpool3d, ds_avgpool3d_f, ds_upsample3d, ds_upsample_f
 """
 from typing import Any
 import pathlib
@@ -28,7 +39,7 @@ from ..._native import DS_LOAD_AVGPOOL2, DS_LOAD_PLAIN, DS_LOAD_UPSAMPLE2
 from . import precision
 from . import runtime
 from .punetg import _AffineHolder, _Attn, _CircConv, _Fourier, make_conv
-from .runtime import AmaxArena, Workspace, require_eval, shift_rows, weights_signature
+from .runtime import AmaxArena, Workspace, _amax_kw, require_eval, shift_rows, weights_signature
 
 _FIELDS = dict(
     input_channels=1, output_channels=1, dimension=2, model_channels=64, time_embed_dim=64,
@@ -129,6 +140,19 @@ def resample_factor(f, what):
     if not ok:
         raise ValueError(f"{what}={f!r}: diffsci_amd ADM resamples by an integer factor >= 1")
     return int(f)
+
+
+def _v4(t):
+    """The (C, spatial...) kernels see volumes as [B, C, D*H, W]."""
+    return t if t.dim() == 4 else t.view(t.shape[0], t.shape[1], -1, t.shape[-1])
+
+
+def _pack_attn(att, conv_precision):
+    """The in and out projections of an _Attn as 1x1 convolutions: fp16x3, or exact fp32 under any other conv_precision."""
+    m, E = att.mhattn, att.mhattn.embed_dim
+    prec = "fp16x3" if conv_precision == "fp16x3" else "fp32"
+    return (ops.pack_conv(m.in_proj_weight.detach().reshape(3 * E, E, 1, 1), prec),
+            ops.pack_conv(m.out_proj.weight.detach().reshape(E, E, 1, 1), prec))
 
 
 class _Block(torch.nn.Module):
@@ -233,14 +257,12 @@ class ADMBaseBlock(torch.nn.Module):
                     pk[id(m)] = ops.pack_conv(w, self.conv_precision, upsampled=False)
                 elif self.conv_precision == "fp16x3" and min(w.shape[0], w.shape[1]) > 4:
                     pk[id(m)] = ops.pack_conv3d(w)
-            prec = "fp16x3" if self.conv_precision == "fp16x3" else "fp32"
             if self.has_residual:
                 w = self.convresidual.weight.detach()
-                pk[id(self.convresidual)] = ops.pack_conv(w.reshape(w.shape[0], w.shape[1], 1, 1).contiguous(), prec)
+                pk[id(self.convresidual)] = ops.pack_conv(w.reshape(w.shape[0], w.shape[1], 1, 1).contiguous(),
+                                                          "fp16x3" if self.conv_precision == "fp16x3" else "fp32")
             if self.has_attn:
-                m, E = self.attn.mhattn, self.attn.mhattn.embed_dim
-                pk["in"] = ops.pack_conv(m.in_proj_weight.detach().reshape(3 * E, E, 1, 1), prec)
-                pk["out"] = ops.pack_conv(m.out_proj.weight.detach().reshape(E, E, 1, 1), prec)
+                pk["in"], pk["out"] = _pack_attn(self.attn, self.conv_precision)
         self._packed, self._packed_sig = pk, sig
         return pk
 
@@ -270,66 +292,50 @@ class ADMBaseBlock(torch.nn.Module):
         if Ci != self.channels_in_modified:
             raise ValueError(f"expected {self.channels_in_modified} input channels, got {Ci}")
         down, up = self.image_sample == "downsample", self.image_sample == "upsample"
+        f = self.image_sample_factor                 # x2: the fused loaders where they exist; any other factor: resampling kernels
         pk = self._packs()
         k1, k2 = self.kinds
         Co = self.channels_out
 
-        def v4(t):                                   # the (C, spatial...) kernels see volumes as [B, C, D*H, W]
-            return t if t.dim() == 4 else t.view(t.shape[0], t.shape[1], -1, t.shape[-1])
-
-        def pool(t):                                 # AvgPool(2) of a field or a volume
-            if t.dim() == 4:
-                return ops.gnorm1_apply(t, None, None, None, 2, pool=True)
-            return ops.avgpool3d(t)
+        def pool(t):                                 # AvgPool(f) of a field or a volume
+            if f != 2:
+                return ops.avgpool_f(t, f)
+            return ops.gnorm1_apply(t, None, None, None, 2, pool=True) if t.dim() == 4 else ops.avgpool3d(t)
 
         film = ops.linear(te.to(x).contiguous(), self.embed_linear.weight, self.embed_linear.bias)      # [B or 1, 2*Cout]
         # first_block (adm.py:315-322): norm1 -> act -> resample -> conv1
         st = ops.gnorm1_stats(x, k1, eps=1e-5)
-        f = self.image_sample_factor
-        if (down or up) and f != 2:
-            # any other factor: the norm pass pools by f itself (fields) or is followed by the resampling kernel, then a
-            # plain conv1 -- the fused x2 loaders stay the factor-2 route
-            if down and self.dimension == 2:
-                a = ops.gnorm1_apply_poolf(x, st, self.norm1.weight, self.norm1.bias, k1, f)
-            else:
-                a = ops.gnorm1_apply(v4(x), st, self.norm1.weight, self.norm1.bias, k1).view(x.shape)
-                a = ops.avgpool_f(a, f) if down else ops.upsample_f(a, f)
-            y = self._conv3(self.conv1, a, pk)
+        if down and self.dimension == 2:             # the norm pass pools itself
+            a = (ops.gnorm1_apply_poolf(x, st, self.norm1.weight, self.norm1.bias, k1, f) if f != 2 else
+                 ops.gnorm1_apply(x, st, self.norm1.weight, self.norm1.bias, k1, pool=True))
         else:
-            fuse_pool = down and self.dimension == 2
-            a = ops.gnorm1_apply(v4(x), st, self.norm1.weight, self.norm1.bias, k1, pool=fuse_pool)
-            if down and self.dimension == 3:
-                a = ops.avgpool3d(a.view(x.shape))
-            elif self.dimension == 3:
-                a = a.view(x.shape)
-            y = self._conv3(self.conv1, a, pk, up=up)
+            a = ops.gnorm1_apply(_v4(x), st, self.norm1.weight, self.norm1.bias, k1).view(x.shape)
+            if down:
+                a = pool(a)
+            elif up and f != 2:
+                a = ops.upsample_f(a, f)
+        y = self._conv3(self.conv1, a, pk, up=up and f == 2)
         # norm2 -> FiLM -> act -> conv2 (adm.py:306-308,324-329)
         st2 = ops.gnorm1_stats(y, k2, eps=1e-5)
-        a2 = ops.gnorm1_apply(v4(y), st2, self.norm2.weight, self.norm2.bias, k2, film=film).view(y.shape)
+        a2 = ops.gnorm1_apply(_v4(y), st2, self.norm2.weight, self.norm2.bias, k2, film=film).view(y.shape)
         r = None
-        if self.has_residual and (down or up) and f != 2:
+        if self.has_residual:                        # convresidual(resample(x)), adm.py:345-349
             m = self.convresidual
-            xr = ops.avgpool_f(x, f) if down else x
-            r = ops.conv(v4(xr), pk[id(m)], bias=m.bias).view((B, Co) + tuple(xr.shape[2:]))
-            if up:                                   # a 1x1 convolution commutes with nearest upsampling: project at low resolution
-                r = ops.upsample_f(r, f)
-        elif self.has_residual:                      # convresidual(resample(x)), adm.py:345-349
             xr = pool(x) if down else x
-            m = self.convresidual
-            if up and self.dimension == 2:           # nearest x2 in the 1x1 convolution's loader
+            if up and f == 2 and self.dimension == 2:                # nearest x2 in the 1x1 convolution's loader
                 r = ops.conv(xr, pk[id(m)], bias=m.bias, load_mode=DS_LOAD_UPSAMPLE2)
-            else:
-                r = ops.conv(v4(xr), pk[id(m)], bias=m.bias).view((B, Co) + tuple(xr.shape[2:]))
-                if up:                               # a 1x1x1 convolution commutes with nearest upsampling: project at low resolution
-                    r = ops.upsample3d(r)
+            else:                                    # a 1x1(x1) convolution commutes with nearest upsampling: project at low resolution
+                r = ops.conv(_v4(xr), pk[id(m)], bias=m.bias).view((B, Co) + tuple(xr.shape[2:]))
+                if up:
+                    r = ops.upsample_f(r, f) if f != 2 else ops.upsample3d(r)
         out = self._conv3(self.conv2, a2, pk, res1=r)
         if self.has_attn:                            # N-dimensional attention over the flattened positions, attention.py:67-102
             E, L = Co, out.numel() // (B * Co)
             mh = self.attn.mhattn
-            qkv = ops.conv(v4(out), pk["in"], bias=mh.in_proj_bias)
+            qkv = ops.conv(_v4(out), pk["in"], bias=mh.in_proj_bias)
             o = ops.attention(qkv.view(B, 3 * E, L), E, precision=self.conv_precision, heads=mh.num_heads)
-            out = ops.conv(o.view(v4(out).shape), pk["out"], bias=mh.out_proj.bias,
-                           res1=v4(out) if self.attn_residual else None).view(out.shape)
+            out = ops.conv(o.view(_v4(out).shape), pk["out"], bias=mh.out_proj.bias,
+                           res1=_v4(out) if self.attn_residual else None).view(out.shape)
         return out
 
 
@@ -742,22 +748,14 @@ class ADM(torch.nn.Module):
                 if self.exact_input_layer:
                     pk[(id(self.input_layer), "exact")] = ops.pack_conv(self.input_layer.weight.detach(), "fp32")
             for a in attns:
-                E = a.mhattn.embed_dim
-                prec = "fp16x3" if self.conv_precision == "fp16x3" else "fp32"
-                pk[(id(a), "in")] = ops.pack_conv(a.mhattn.in_proj_weight.detach().reshape(3 * E, E, 1, 1), prec)
-                pk[(id(a), "out")] = ops.pack_conv(a.mhattn.out_proj.weight.detach().reshape(E, E, 1, 1), prec)
+                pk[(id(a), "in")], pk[(id(a), "out")] = _pack_attn(a, self.conv_precision)
         self._packed, self._packed_sig = pk, sig
         return pk
 
     # ------------------------------------------------------------------ the network
-    def _amax_kw(self, m_or_pack, pk=None, **kw):
-        """in_amax / out_amax are arguments of the fp16x3 kernels only."""
-        p = m_or_pack if pk is None else pk[id(m_or_pack)]
-        return kw if p.kind == "fp16x3" else {}
-
     def _conv(self, m, x, pk, in_amax=None, out_amax=None, **kw):
         return ops.conv(x, pk[id(m)], bias=m.bias, circular=isinstance(m, _CircConv),
-                        **self._amax_kw(m, pk, in_amax=in_amax, out_amax=out_amax), **kw)
+                        **_amax_kw(pk[id(m)], in_amax=in_amax, out_amax=out_amax), **kw)
 
     def _raw_amax(self, x, xa):
         """in_amax of a launch that reads the raw tensor x: the row its producer left, else a reduction into a row."""
@@ -773,6 +771,10 @@ class ADM(torch.nn.Module):
 
     def _fused(self):
         return self.fuse_norm and self.conv_precision == "fp16x3"
+
+    def _folds(self, C):
+        """The norm in front of a C-channel convolution is folded into its loader (per layer: see PUNetG.fuse_max_cot)."""
+        return self._fused() and (C + 63) // 64 <= self.fuse_max_cot
 
     def _stats_buf(self, ws, B, C, H, W, dev):
         if not self._fused():
@@ -791,141 +793,138 @@ class ADM(torch.nn.Module):
         xs: tile statistics of x -- one buffer, or a pair when x is the channel concatenation of two
         convolution outputs -- or None (then norm1 runs as standalone kernels).  xa: the amax row of x (convresidual reads
         the raw x), out_amax: a zeroed row for the result's (see PUNetG.forward_with_shifts)."""
-        B, Ci, H, W = x.shape
-        dev = x.device
-        down, up = blk.sample == "down", blk.sample == "up"
-        k1, k2 = blk.kinds                                     # 0 GroupNorm(1, C), 1 GroupRMSNorm(1, C)
-        f = blk.factor
-        Ho, Wo = (H // f, W // f) if down else ((f * H, f * W) if up else (H, W))
-        resample_f = (down or up) and f != 2       # any other factor: resampling kernels around plain convolutions
-        mode = DS_LOAD_UPSAMPLE2 if up else DS_LOAD_PLAIN
-        fused = self._fused()
-        fuse1 = fused and (Ci + 63) // 64 <= self.fuse_max_cot            # per layer: see PUNetG.fuse_max_cot
-        fuse2 = fused and (blk.cout + 63) // 64 <= self.fuse_max_cot
-        ys = self._stats_buf(ws, B, blk.cout, Ho, Wo, dev)
-        # first_block: norm1 -> act -> resample -> conv1                          (adm.py:312-323)
-        # not for 'down' (pooling follows the activation) nor 'up' blocks (the loader would activate every source
-        # pixel four times, once per upsampled copy)
-        if fuse1 and xs is not None and not down and not up:
-            sa, sb = xs if isinstance(xs, tuple) else (xs, None)
-            tab = ws.take((B, ops.table_channels(Ci), 4), dev)
-            ops.gnorm1_table(sa, blk.norm1.weight, blk.norm1.bias, k1, Ci * H * W, stats_b=sb, eps=1e-5, out=tab)   # + the activation's exponent
-            y = self._conv(blk.conv1, x, pk, load_mode=mode, prenorm=tab, tile_stats=ys,
-                           out=ws.take((B, blk.cout, Ho, Wo), dev))
-            ws.give(tab)
-        else:                                                                     # pooling follows the activation
-            Hm, Wm = (Ho, Wo) if down else (H, W)
-            stats = ws.take((B, 2), dev)
-            scratch = ws.take((ops.N.lib().ds_gnorm1_workspace_bytes(B) // 4,), dev)
-            if xs is not None and self.tile_stats_norms:   # the producers left tile statistics: no pass over x
-                sa, sb = xs if isinstance(xs, tuple) else (xs, None)
-                ops.gnorm1_stats_tiles(sa, k1, Ci * H * W, stats_b=sb, eps=1e-5, stats=stats)
-            else:
-                ops.gnorm1_stats(x, k1, eps=1e-5, stats=stats, workspace=scratch)
-            if resample_f:
-                # the norm pass pools by f itself ('down'), or the upsampling pass follows it at low resolution ('up'); the
-                # fused x2 loaders, parity kernels and image forms serve f = 2 only (DESIGN 4.7)
-                if down:
-                    a = ops.gnorm1_apply_poolf(x, stats, blk.norm1.weight, blk.norm1.bias, k1, f, out=ws.take((B, Ci, Ho, Wo), dev))
-                else:
-                    a = ops.gnorm1_apply(x, stats, blk.norm1.weight, blk.norm1.bias, k1, out=ws.take((B, Ci, H, W), dev))
-                ia = self._normed_amax(blk, a)                                  # nearest upsampling keeps max |a|
-                if up:
-                    au = ops.upsample_f(a, f, out=ws.take((B, Ci, Ho, Wo), dev))
-                    ws.give(a)
-                    a = au
-                y = self._conv(blk.conv1, a, pk, tile_stats=ys, out=ws.take((B, blk.cout, Ho, Wo), dev), in_amax=ia)
-                ws.give(a)
-            elif not up and self._norm_images_ok(blk.conv1, pk, Ci):
-                # the standalone norm writes the convolution's pre-split fp16 images, staged there by LDS-DMA (see punetg._res)
-                img = ops.gnorm1_apply_images(x, stats, blk.norm1.weight, blk.norm1.bias, k1, pool=down,
-                                              out=ws.take((ops.conv_images_floats(B, Ci, Hm, Wm),), dev))
-                y = ops.conv_img(img, pk[id(blk.conv1)], B, Ci, Hm, Wm, bias=blk.conv1.bias, tile_stats=ys,
-                                 out=ws.take((B, blk.cout, Ho, Wo), dev))
-                ws.give(img)
-            elif up and self.norm_images and not isinstance(blk.conv1, _CircConv) \
-                    and ops.conv_up_img_supported(pk[id(blk.conv1)], H, W):
-                # the same for the parity kernels of conv1(nearest_x2(.)): images of the low-resolution activation
-                img = ops.gnorm1_apply_images(x, stats, blk.norm1.weight, blk.norm1.bias, k1,
-                                              out=ws.take((ops.conv_images_floats(B, Ci, H, W),), dev))
-                y = ops.conv_up_img(img, pk[id(blk.conv1)], B, Ci, H, W, bias=blk.conv1.bias, tile_stats=ys,
-                                    out=ws.take((B, blk.cout, Ho, Wo), dev))
-                ws.give(img)
-            else:
-                a = ops.gnorm1_apply(x, stats, blk.norm1.weight, blk.norm1.bias, k1, pool=down,
-                                     out=ws.take((B, Ci, Hm, Wm), dev))
-                y = self._conv(blk.conv1, a, pk, load_mode=mode, tile_stats=ys, out=ws.take((B, blk.cout, Ho, Wo), dev),
-                               in_amax=self._normed_amax(blk, a))
-                ws.give(a)
-            ws.give(stats)
-            ws.give(scratch)
-        # residual_block: convresidual(resample(x))                               (adm.py:345-349)
-        r_up = False
-        raw = self._raw_amax(x, xa) if pk[id(blk.convresidual)].kind == "fp16x3" else None       # pooling / upsampling keep max |x| a bound
-        if down and resample_f:
-            a = ops.avgpool_f(x, f, out=ws.take((B, Ci, Ho, Wo), dev))
-            r = self._conv(blk.convresidual, a, pk, out=ws.take((B, blk.cout, Ho, Wo), dev), in_amax=raw)
-            ws.give(a)
-        elif up and resample_f:                  # project at low resolution, then upsample the projection
-            a = self._conv(blk.convresidual, x, pk, out=ws.take((B, blk.cout, H, W), dev), in_amax=raw)
-            r = ops.upsample_f(a, f, out=ws.take((B, blk.cout, Ho, Wo), dev))
-            ws.give(a)
-        elif down and pk[id(blk.convresidual)].kind == "fp16x3":
-            r = self._conv(blk.convresidual, x, pk, load_mode=DS_LOAD_AVGPOOL2, out=ws.take((B, blk.cout, Ho, Wo), dev), in_amax=raw)
-        elif down:
-            a = ops.gnorm1_apply(x, None, None, None, 2, pool=True, out=ws.take((B, Ci, Ho, Wo), dev))
-            r = self._conv(blk.convresidual, a, pk, out=ws.take((B, blk.cout, Ho, Wo), dev))
-            ws.give(a)
-        elif up and pk[id(blk.convresidual)].kind == "fp16x3" and pk[id(blk.conv2)].kind == "fp16x3":
-            # a 1x1 convolution commutes with nearest upsampling: project at low resolution (a quarter of the
-            # pixels) and let conv2's epilogue add the result upsampled
-            r = self._conv(blk.convresidual, x, pk, out=ws.take((B, blk.cout, H, W), dev), in_amax=raw)
-            r_up = True
-        else:
-            r = self._conv(blk.convresidual, x, pk, load_mode=mode, out=ws.take((B, blk.cout, Ho, Wo), dev), in_amax=raw)
-        # norm2 -> FiLM -> act -> conv2, + residual                               (adm.py:325-337)
+        y, ys = self._norm1_conv1(blk, x, xs, pk, ws)
+        r, r_up = self._residual(blk, x, xa, pk, ws)
         has_attn = hasattr(blk, "attn")
-        os_ = self._stats_buf(ws, B, blk.cout, Ho, Wo, dev) if (want_stats and not has_attn) else None
-        h3 = self._am is not None
-        oa = (self._am.row() if has_attn else out_amax) if h3 else None            # conv2's result feeds the attention, or is the block's
-        if fuse2:
-            tab = ws.take((B, ops.table_channels(blk.cout), 4), dev)
-            ops.gnorm1_table(ys, blk.norm2.weight, blk.norm2.bias, k2, blk.cout * Ho * Wo, film=film, eps=1e-5, out=tab)
-            out = self._conv(blk.conv2, y, pk, res1=r, res1_upsampled=r_up, prenorm=tab, tile_stats=os_,
-                             out=ws.take((B, blk.cout, Ho, Wo), dev), out_amax=oa)
-            ws.give(tab)
-            ws.give(ys)
-            ws.give(y)
-        else:
-            stats = ws.take((B, 2), dev)
-            scratch = ws.take((ops.N.lib().ds_gnorm1_workspace_bytes(B) // 4,), dev)
-            if ys is not None and self.tile_stats_norms:
-                ops.gnorm1_stats_tiles(ys, k2, blk.cout * Ho * Wo, eps=1e-5, stats=stats)
-            else:
-                ops.gnorm1_stats(y, k2, eps=1e-5, stats=stats, workspace=scratch)
-            if self._norm_images_ok(blk.conv2, pk, blk.cout):
-                img = ops.gnorm1_apply_images(y, stats, blk.norm2.weight, blk.norm2.bias, k2, film=film,
-                                              out=ws.take((ops.conv_images_floats(B, blk.cout, Ho, Wo),), dev))
-                out = ops.conv_img(img, pk[id(blk.conv2)], B, blk.cout, Ho, Wo, bias=blk.conv2.bias, res1=r,
-                                   res1_upsampled=r_up, tile_stats=os_, out=y, out_amax=oa)
-                ws.give(img)
-            else:
-                a2 = ops.gnorm1_apply(y, stats, blk.norm2.weight, blk.norm2.bias, k2, film=film,
-                                      out=ws.take((B, blk.cout, Ho, Wo), dev))
-                out = self._conv(blk.conv2, a2, pk, res1=r, res1_upsampled=r_up, tile_stats=os_, out=y,
-                                 in_amax=self._normed_amax(blk, a2), out_amax=oa)
-                ws.give(a2)
-            ws.give(stats)
-            ws.give(scratch)
-            if ys is not None:
-                ws.give(ys)
-        ws.give(r)
+        oa = None if self._am is None else (self._am.row() if has_attn else out_amax)   # conv2's result feeds the attention, or is the block's
+        out, os_ = self._norm2_conv2(blk, y, ys, film, r, r_up, pk, ws, want_stats and not has_attn, oa)
         if has_attn:
-            os_ = self._stats_buf(ws, B, blk.cout, Ho, Wo, dev) if want_stats else None
+            os_ = self._stats_buf(ws, *out.shape, out.device) if want_stats else None
             out2 = self._attention(blk.attn, out, pk, ws, tile_stats=os_, in_amax=oa, out_amax=out_amax)
             ws.give(out)
             out = out2
         return out, os_
+
+    def _norm1_conv1(self, blk, x, xs, pk, ws):
+        """first_block: norm1 -> act -> resample -> conv1 (adm.py:312-323) -> (y, the tile statistics conv1 left or None)."""
+        B, Ci, H, W = x.shape
+        down, up = blk.sample == "down", blk.sample == "up"
+        f = blk.factor
+        Ho, Wo = (H // f, W // f) if down else ((f * H, f * W) if up else (H, W))
+        ys = self._stats_buf(ws, B, blk.cout, Ho, Wo, x.device)
+        # folded into conv1's loader -- not in 'down' blocks (pooling follows the activation) nor in 'up' blocks (the loader would
+        # activate every source pixel four times, once per upsampled copy)
+        if not (self._folds(Ci) and xs is not None and not down and not up):
+            return self._norm_conv(blk, blk.norm1, blk.kinds[0], blk.conv1, x, xs, pk, ws, down=down, up=up, tile_stats=ys), ys
+        sa, sb = xs if isinstance(xs, tuple) else (xs, None)
+        tab = ws.take((B, ops.table_channels(Ci), 4), x.device)
+        ops.gnorm1_table(sa, blk.norm1.weight, blk.norm1.bias, blk.kinds[0], Ci * H * W, stats_b=sb, eps=1e-5, out=tab)   # + the activation's exponent
+        y = self._conv(blk.conv1, x, pk, prenorm=tab, tile_stats=ys, out=ws.take((B, blk.cout, Ho, Wo), x.device))
+        ws.give(tab)
+        return y, ys
+
+    def _residual(self, blk, x, xa, pk, ws):
+        """residual_block: convresidual(resample(x)) (adm.py:345-349) -> (r, whether conv2's epilogue is to add r upsampled x2).
+        Pooling happens in the 1x1 convolution's loader (x2, fp16x3) or in a pass in front of it; a 1x1 convolution commutes
+        with nearest upsampling, so 'up' blocks project at low resolution (a quarter of the pixels) and conv2's epilogue (x2,
+        fp16x3 on both) or the resampling kernel upsamples the projection -- else the loader upsamples."""
+        B, Ci, H, W = x.shape
+        dev, m, f = x.device, blk.convresidual, blk.factor
+        down, up = blk.sample == "down", blk.sample == "up"
+        lo, hi = (H, W), ((H // f, W // f) if down else ((f * H, f * W) if up else (H, W)))
+        h3 = pk[id(m)].kind == "fp16x3"
+        raw = self._raw_amax(x, xa) if h3 else None                  # pooling / upsampling keep max |x| a bound
+
+        def conv(t, sides, **kw):
+            return self._conv(m, t, pk, out=ws.take((B, blk.cout) + sides, dev), in_amax=raw, **kw)
+
+        if down and (f != 2 or not h3):
+            a = (ops.avgpool_f(x, f, out=ws.take((B, Ci) + hi, dev)) if f != 2 else
+                 ops.gnorm1_apply(x, None, None, None, 2, pool=True, out=ws.take((B, Ci) + hi, dev)))
+            r = conv(a, hi)
+            ws.give(a)
+            return r, False
+        if down:
+            return conv(x, hi, load_mode=DS_LOAD_AVGPOOL2), False
+        if up and f != 2:
+            a = conv(x, lo)
+            r = ops.upsample_f(a, f, out=ws.take((B, blk.cout) + hi, dev))
+            ws.give(a)
+            return r, False
+        if up and h3 and pk[id(blk.conv2)].kind == "fp16x3":
+            return conv(x, lo), True
+        return conv(x, hi, load_mode=DS_LOAD_UPSAMPLE2 if up else DS_LOAD_PLAIN), False
+
+    def _norm2_conv2(self, blk, y, ys, film, r, r_up, pk, ws, want_stats, oa):
+        """norm2 -> FiLM -> act -> conv2, + residual (adm.py:325-337) -> (out, its tile statistics or None); y, ys and r go
+        back to the pool (the standalone route writes out over y)."""
+        B, C, H, W = y.shape
+        os_ = self._stats_buf(ws, B, C, H, W, y.device) if want_stats else None
+        kw = dict(res1=r, res1_upsampled=r_up, tile_stats=os_, out_amax=oa)
+        if self._folds(C):
+            tab = ws.take((B, ops.table_channels(C), 4), y.device)
+            ops.gnorm1_table(ys, blk.norm2.weight, blk.norm2.bias, blk.kinds[1], C * H * W, film=film, eps=1e-5, out=tab)
+            out = self._conv(blk.conv2, y, pk, prenorm=tab, out=ws.take((B, C, H, W), y.device), **kw)
+            ws.give(tab)
+            ws.give(ys)
+            ws.give(y)
+        else:
+            out = self._norm_conv(blk, blk.norm2, blk.kinds[1], blk.conv2, y, ys, pk, ws, film=film, out=y, **kw)
+            if ys is not None:
+                ws.give(ys)
+        ws.give(r)
+        return out, os_
+
+    def _norm_conv(self, blk, norm, kind, conv, x, xs, pk, ws, down=False, up=False, film=None, out=None, **conv_kw):
+        """conv(resample(SiLU(FiLM(norm(x))))) with the norm as standalone kernels -- both norm sites of a block.  Statistics from
+        the producers' tile statistics xs (one buffer or the pair of a concatenation) where they were left, else by a pass over x;
+        then the norm pass writes the convolution's pre-split fp16 images, staged there by LDS-DMA (see punetg._res; conv_img, or
+        the parity kernels of conv(nearest_x2(.)) on images of the low-resolution activation), or a buffer for a plain convolution.
+        Resampling by 2 is the norm pass's own pooling / the convolution's loader; by any other factor the norm pass pools by f
+        itself, or the upsampling kernel follows it, around a plain convolution.  out: where the convolution writes
+        (None: a pool buffer); conv_kw: res1, res1_upsampled, tile_stats, out_amax of the convolution."""
+        B, C, H, W = x.shape
+        dev, p = x.device, pk[id(conv)]
+        f = blk.factor
+        by_f = (down or up) and f != 2                                # resampling kernels around a plain convolution
+        Hm, Wm = (H // f, W // f) if down else (H, W)                 # what the norm pass writes
+        Ho, Wo = (f * H, f * W) if up else (Hm, Wm)
+
+        stats = ws.take((B, 2), dev)
+        scratch = ws.take((ops.N.lib().ds_gnorm1_workspace_bytes(B) // 4,), dev)
+        if xs is not None and self.tile_stats_norms:                  # no pass over x
+            sa, sb = xs if isinstance(xs, tuple) else (xs, None)
+            ops.gnorm1_stats_tiles(sa, kind, C * H * W, stats_b=sb, eps=1e-5, stats=stats)
+        else:
+            ops.gnorm1_stats(x, kind, eps=1e-5, stats=stats, workspace=scratch)
+        if by_f:
+            img_conv = None
+        elif up:
+            img_conv = (ops.conv_up_img if self.norm_images and not isinstance(conv, _CircConv) and ops.conv_up_img_supported(p, H, W)
+                        else None)
+        else:
+            img_conv = ops.conv_img if self._norm_images_ok(conv, pk, C) else None
+        if img_conv is not None:
+            img = ops.gnorm1_apply_images(x, stats, norm.weight, norm.bias, kind, pool=down, film=film,
+                                          out=ws.take((ops.conv_images_floats(B, C, Hm, Wm),), dev))
+            y = img_conv(img, p, B, C, Hm, Wm, bias=conv.bias, out=ws.take((B, p.Cout, Ho, Wo), dev) if out is None else out, **conv_kw)
+            ws.give(img)
+        else:
+            if down and by_f:
+                a = ops.gnorm1_apply_poolf(x, stats, norm.weight, norm.bias, kind, f, out=ws.take((B, C, Hm, Wm), dev))
+            else:
+                a = ops.gnorm1_apply(x, stats, norm.weight, norm.bias, kind, pool=down, film=film, out=ws.take((B, C, Hm, Wm), dev))
+            ia = self._normed_amax(blk, a)                            # nearest upsampling keeps max |a|
+            if up and by_f:
+                au = ops.upsample_f(a, f, out=ws.take((B, C, Ho, Wo), dev))
+                ws.give(a)
+                a = au
+            y = self._conv(conv, a, pk, load_mode=DS_LOAD_UPSAMPLE2 if up and not by_f else DS_LOAD_PLAIN, in_amax=ia,
+                           out=ws.take((B, p.Cout, Ho, Wo), dev) if out is None else out, **conv_kw)
+            ws.give(a)
+        ws.give(stats)
+        ws.give(scratch)
+        return y
 
     def _attention(self, att, x, pk, ws, tile_stats=None, in_amax=None, out_amax=None):
         """TwoDimensionalAttention.forward (attention.py:67-72,82-90), channel-major; amax rows as PUNetG._attention."""
@@ -940,109 +939,92 @@ class ADM(torch.nn.Module):
         self.check_field_size(x.shape)
         require_eval(self, self.config.dropout, self.config.cond_dropout)
         pk = self.packed_weights()
-        ws = self._ws
-        cfg = self.config
-        B = x.shape[0]
-        it = iter(range(len(shifts)))
-
-        def film():
-            return shift_rows(shifts[next(it)], row, B)
-
-        dev = x.device
-        H, W = x.shape[2:]
-
-        def give(t, ts):
-            ws.give(t)
-            for q in (ts if isinstance(ts, tuple) else (ts,)):
-                if q is not None:
-                    ws.give(q)
-
+        it = iter(shifts)
         # activation exponents of the raw-input launches (input layer, every block's convresidual, the attention, a wide
         # output layer): rows of one arena per forward, filled by the producers' epilogues -- see PUNetG.forward_with_shifts
         h3 = self.conv_precision == "fp16x3"
-        am = self._am = AmaxArena(ws, B, dev, zero=self.exact_input_layer) if h3 else None     # else zeroed by the input layer's reduction
+        self._am = AmaxArena(self._ws, x.shape[0], x.device, zero=self.exact_input_layer) if h3 else None   # else zeroed by the input layer's reduction
+        try:
+            return self._walk(x, lambda: shift_rows(next(it), row, x.shape[0]), pk, out)
+        finally:
+            if self._am is not None:
+                self._am.release()
+            self._am = None
+
+    def _walk(self, x, film, pk, out):
+        """The network once (adm.py:199-216, 667-675, 764-774, 927-934): stem, encoder layers pushing their results on the skip
+        stack, middle block, decoder layers popping them, output layer.  An activation is PUNetG._walk's record (tensor, the tile
+        statistics its producer left -- the pair of its sources' for a concatenation -- or None, the amax row its producer
+        filled or None).  Every buffer comes from the workspace and goes back as soon as its reader has run; a record on the
+        skip stack belongs to the stack until it is popped and its last reader has run."""
+        ws, cfg, am = self._ws, self.config, self._am
+        B, dev, (H, W) = x.shape[0], x.device, x.shape[2:]
+        final = self.decoder.layers[-1].input_blocks[-1]                    # feeds the output layer: no norm follows, no statistics
 
         def slot():
-            return am.row() if h3 else None
+            return am.row() if am is not None else None
 
-        try:
-            x_amax = (am.of_input(x, precision.input_layer_flag(self, dev), pk[(id(self.input_layer), "wmax")])
-                      if (h3 and not self.exact_input_layer) else None)             # first: this launch also zeroes the arena
-            ha = slot()
-            if h3 and self.exact_input_layer:                                       # see PUNetG.forward_with_shifts
-                hs = None
-                h = ops.conv(x, pk[(id(self.input_layer), "exact")], bias=self.input_layer.bias,
-                             out=ws.take((B, cfg.model_channels, H, W), dev))
-                ops.absmax_rows(h, out=ha)
-            else:
-                hs = self._stats_buf(ws, B, cfg.model_channels, H, W, dev)
-                h = self._conv(self.input_layer, x, pk, tile_stats=hs, out=ws.take((B, cfg.model_channels, H, W), dev),
-                               in_amax=x_amax, out_amax=ha)
-            skips = [(h, hs, ha)]                                                   # adm.py:667-675
-            for lay in self.encoder.layers:
-                for blk in lay.input_blocks:
-                    ha2 = slot()
-                    h2, hs2 = self._block(blk, h, film(), pk, ws, xs=hs, xa=ha, out_amax=ha2)
-                    if not any(h is s for s, _, _ in skips):
-                        give(h, hs)
-                    h, hs, ha = h2, hs2, ha2
-                skips.append((h, hs, ha))
-            for blk in self.middle_block.middle_blocks:
-                ha2 = slot()
-                h2, hs2 = self._block(blk, h, film(), pk, ws, xs=hs, xa=ha, out_amax=ha2)
-                if not any(h is s for s, _, _ in skips):
-                    give(h, hs)
-                h, hs, ha = h2, hs2, ha2
-            nl = len(self.decoder.layers)
+        def give(a):
+            ws.give(a[0])
+            for q in (a[1] if isinstance(a[1], tuple) else (a[1],)):
+                if q is not None:
+                    ws.give(q)
 
-            def join(h, hs, ha, skip, sks, ska):                                     # adm.py:297-304
-                if cfg.skip_integration_type == "concat":
-                    hc = ops.concat2(h, skip, out=ws.take((B, h.shape[1] + skip.shape[1]) + tuple(h.shape[2:]), dev))
-                    hca = ops.amax_merge(slot(), ha, ska) if h3 else None           # max over the two halves
-                    return hc, ((hs, sks) if (hs is not None and sks is not None) else None), hca   # statistics of a concat are additive
-                hc = ops.add(h, skip, out=ws.take(h.shape, dev))
-                return hc, None, (am.of(hc) if h3 else None)
+        def join(a, s):                                                      # adm.py:297-304
+            if cfg.skip_integration_type == "concat":
+                hc = ops.concat2(a[0], s[0], out=ws.take((B, a[0].shape[1] + s[0].shape[1]) + tuple(a[0].shape[2:]), dev))
+                hca = ops.amax_merge(slot(), a[2], s[2]) if am is not None else None          # max over the two halves
+                return hc, ((a[1], s[1]) if (a[1] is not None and s[1] is not None) else None), hca   # statistics of a concat are additive
+            hc = ops.add(a[0], s[0], out=ws.take(a[0].shape, dev))
+            return hc, None, (am.of(hc) if am is not None else None)
 
-            for li, lay in enumerate(self.decoder.layers):                          # adm.py:764-774, 927-934
-                skip, sks, ska = skips.pop()
-                nblk = len(lay.input_blocks)
-                if cfg.decoder_type == 1:
-                    hc, hcs, hca = join(h, hs, ha, skip, sks, ska)
-                    pending = [(h, hs)] + ([(skip, sks)] if skip is not h else [])     # statistics are read by block 0's table
-                    for j, blk in enumerate(lay.input_blocks):
-                        final = li == nl - 1 and j == nblk - 1                        # feeds the output layer: no norm follows
-                        ha2 = slot()
-                        h2, hs2 = self._block(blk, hc, film(), pk, ws, xs=hcs, want_stats=not final, xa=hca, out_amax=ha2)
-                        if j == 0:
-                            ws.give(hc)
-                            for t, ts in pending:
-                                give(t, ts)
-                        else:
-                            give(hc, hcs)
-                        hc, hcs, hca = h2, hs2, ha2
-                    h, hs, ha = hc, hcs, hca
-                else:                                                               # every block joins the skip (adm.py:848-851)
-                    for j, blk in enumerate(lay.input_blocks):
-                        final = li == nl - 1 and j == nblk - 1
-                        hc, hcs, hca = join(h, hs, ha, skip, sks, ska)
-                        ha2 = slot()
-                        h2, hs2 = self._block(blk, hc, film(), pk, ws, xs=hcs, want_stats=not final, xa=hca, out_amax=ha2)
-                        ws.give(hc)
-                        if h is not skip:
-                            give(h, hs)
-                        h, hs, ha = h2, hs2, ha2
-                    give(skip, sks)
-            for s_, ss, _ in skips:                                                  # the stem copy is never consumed
-                if s_ is not h:
-                    give(s_, ss)
-            m = self.output_layer
-            if m.out_channels <= 4:                              # see PUNetG._out_conv
-                y = ops.conv_direct(h, m.weight, m.bias, out=out)
-            else:
-                y = self._conv(m, h, pk, out=out, in_amax=ha)
-            give(h, hs)
-            return y
-        finally:
-            if am is not None:
-                am.release()
-            self._am = None
+        def chain(blocks, a, stacked=False, skip=None, joins=0):
+            """a through residual blocks, each input given back once its block has run -- except the first when the skip stack
+            owns it (`stacked`).  The first `joins` blocks read join(a, skip) instead (decoder_type 1: the first one, adm.py:764-774;
+            2: every one, :848-851); a join's tensor goes back after its block, its statistics with the sources they belong to,
+            and the skip after the last join that read it."""
+            for j, blk in enumerate(blocks):
+                src = None
+                if j < joins:
+                    src, a = a, join(a, skip)
+                ha = slot()
+                a2 = self._block(blk, a[0], film(), pk, ws, xs=a[1], want_stats=blk is not final, xa=a[2], out_amax=ha) + (ha,)
+                if src is not None:
+                    ws.give(a[0])
+                    give(src)
+                    if j == joins - 1:
+                        give(skip)
+                elif j or not stacked:
+                    give(a)
+                a = a2
+            return a
+
+        x_amax = (am.of_input(x, precision.input_layer_flag(self, dev), pk[(id(self.input_layer), "wmax")])
+                  if (am is not None and not self.exact_input_layer) else None)      # first: this launch also zeroes the arena
+        ha = slot()
+        if am is not None and self.exact_input_layer:                               # see PUNetG.forward_with_shifts
+            hs = None
+            h = ops.conv(x, pk[(id(self.input_layer), "exact")], bias=self.input_layer.bias,
+                         out=ws.take((B, cfg.model_channels, H, W), dev))
+            ops.absmax_rows(h, out=ha)
+        else:
+            hs = self._stats_buf(ws, B, cfg.model_channels, H, W, dev)
+            h = self._conv(self.input_layer, x, pk, tile_stats=hs, out=ws.take((B, cfg.model_channels, H, W), dev),
+                           in_amax=x_amax, out_amax=ha)
+        a = h, hs, ha
+        skips = [a]                                                                 # adm.py:667-675
+        for lay in self.encoder.layers:
+            a = chain(lay.input_blocks, a, stacked=True)
+            skips.append(a)
+        a = chain(self.middle_block.middle_blocks, a, stacked=True)                 # never empty (ADMConfig.middle_block_attn_config)
+        for lay in self.decoder.layers:
+            a = chain(lay.input_blocks, a, skip=skips.pop(), joins=1 if cfg.decoder_type == 1 else len(lay.input_blocks))
+        for s in skips:                                                             # the stem copy is never consumed
+            give(s)
+        m = self.output_layer
+        if m.out_channels <= 4:                                                     # see PUNetG._out_conv
+            y = ops.conv_direct(a[0], m.weight, m.bias, out=out)
+        else:
+            y = self._conv(m, a[0], pk, out=out, in_amax=a[2])
+        give(a)
+        return y

@@ -26,7 +26,7 @@ from ... import ops
 from ..._native import DS_LOAD_MAXPOOL2, DS_LOAD_UPSAMPLE2
 from . import precision, runtime
 from .punetg_config import PUNetGConfig, scale_factor
-from .runtime import AmaxArena, Workspace, require_eval, shift_rows, weights_signature
+from .runtime import AmaxArena, Workspace, _amax_kw, require_eval, shift_rows, weights_signature
 
 POOL_ROUTES = ("loader", "pass", "epilogue")
 POOL_ROUTE_DEFAULT = "epilogue"
@@ -588,12 +588,13 @@ class PUNetG(torch.nn.Module):
         a1 = fs.am.row() if fs.am is not None else None
         a2 = fs.am.row() if fs.am is not None else None
         h = ops.conv(te, pk[id(n[0])], bias=n[0].bias, out=ws.take((B, n[0].out_features, H, W), dev),
-                     **self._amax_kw(in_amax=a0, out_amax=a1))
+                     **_amax_kw(pk[id(n[0])], in_amax=a0, out_amax=a1))
         ops.inorm_silu(h, None, None, kind=2, out=h)                 # |SiLU(v)| <= |v|: a1 stays a valid bound
         h2 = ops.conv(h, pk[id(n[2])], bias=n[2].bias, out=ws.take((B, n[2].out_features, H, W), dev),
-                      **self._amax_kw(in_amax=a1, out_amax=a2))
+                      **_amax_kw(pk[id(n[2])], in_amax=a1, out_amax=a2))
         ops.inorm_silu(h2, None, None, kind=2, out=h2)
-        out = ops.conv(h2, pk[id(n[4])], bias=n[4].bias, out=ws.take((B, n[4].out_features, H, W), dev), **self._amax_kw(in_amax=a2))
+        out = ops.conv(h2, pk[id(n[4])], bias=n[4].bias, out=ws.take((B, n[4].out_features, H, W), dev),
+                       **_amax_kw(pk[id(n[4])], in_amax=a2))
         ws.give(h)
         ws.give(h2)
         return out                                                   # volumes: [B, C_block, D*H, W], viewed by the caller
@@ -782,12 +783,8 @@ class PUNetG(torch.nn.Module):
         return pk
 
     # ------------------------------------------------------------------ the network
-    def _amax_kw(self, **kw):
-        """in_amax / out_amax are arguments of the fp16x3 kernels only."""
-        return kw if self.conv_precision == "fp16x3" else {}
-
     def _conv(self, m, x, pk, in_amax=None, out_amax=None, **kw):
-        return ops.conv(x, pk[id(m)], bias=m.bias, circular=self.circular, **self._amax_kw(in_amax=in_amax, out_amax=out_amax), **kw)
+        return ops.conv(x, pk[id(m)], bias=m.bias, circular=self.circular, **_amax_kw(pk[id(m)], in_amax=in_amax, out_amax=out_amax), **kw)
 
     def _out_is_direct(self, m):
         return m.out_channels <= 4 and getattr(self, "direct_out", True) and self.config.in_out_kernel_size == 3
@@ -797,7 +794,7 @@ class PUNetG(torch.nn.Module):
         padding Cout to a 64-channel MFMA tile."""
         if self._out_is_direct(m):
             return ops.conv_direct(h, pk.get((id(m), "eff"), m.weight), m.bias, circular=circular, out=out)
-        return ops.conv(h, pk[id(m)], bias=m.bias, circular=circular, out=out, **self._amax_kw(in_amax=in_amax))
+        return ops.conv(h, pk[id(m)], bias=m.bias, circular=circular, out=out, **_amax_kw(pk[id(m)], in_amax=in_amax))
 
     def _fused(self):
         return self.fuse_norm and self.conv_precision == "fp16x3"

@@ -1,6 +1,6 @@
-"""A whole PUNetG forward through the recording stand-in of tests/abi_trace.py, on the host, and the table of network
-configurations whose records are pinned (tests/golden/net_trace.json.gz, written by tools/make_net_trace_golden.py from the
-PARENT commit's diffsci_amd/).  A record holds, per case, every launch (entry point, arguments, pointers as [label, byte
+"""A whole PUNetG or ADM forward (or one stand-alone ADM block) through the recording stand-in of tests/abi_trace.py, on the host,
+and the tables of network configurations whose records are pinned (TABLES: tests/golden/<table>.json.gz, written by
+tools/make_net_trace_golden.py from the PARENT commit's diffsci_amd/).  A record holds, per case, every launch (entry point, arguments, pointers as [label, byte
 offset]) and, among them, every return of a buffer to the pool; how many pool buffers were taken and how many never given back; and a digest of every pool buffer ATen wrote
 (fill_, copy_, torch.add(out=)): kernels do not run, so a pool buffer holds its take number + 1 until torch itself writes it.
 No RNG: parameters, buffers and inputs are filled from the arithmetic pattern of abi_trace.Ctx.f, so the packed weights' shift
@@ -17,6 +17,9 @@ B = 2
 BASE = dict(input_channels=2, output_channels=1, model_channels=16, channel_expansion=(2,), number_resnet_downward_block=2,
             number_resnet_upward_block=2, number_resnet_attn_block=2, number_resnet_before_attn_block=1,
             number_resnet_after_attn_block=1)
+ADM_BASE = dict(input_channels=2, output_channels=1, model_channels=16, time_embed_dim=8, output_embed_dim=16, channel_expansion=(2,),
+                number_resnet_downward_block=2, number_resnet_upward_block=2, number_resnet_attn_block=2,
+                number_resnet_before_attn_block=1, number_resnet_after_attn_block=1)
 PC = "ds_conv2d_h3_pc"
 
 
@@ -88,29 +91,46 @@ class Half(torch.nn.Module):
         return x * 0.5
 
 
+def punetg(dim, cls="PUNetG", cls_args=(), **cfg):
+    """A network family: -> the network of one case and the switches it gets whatever the environment says."""
+    from diffsci_amd.models.nets import punetg as nets
+    from diffsci_amd.models.nets.punetg_config import PUNetGConfig
+    config = PUNetGConfig(**{**BASE, "dimension": dim, **cfg})
+    return getattr(nets, cls)(config, *cls_args), dict(pool_route="epilogue", norm_images=True)
+
+
+def adm(dim, cls_args=(), **cfg):
+    from diffsci_amd.models.nets import adm as nets
+    return nets.ADM(nets.ADMConfig(**{**ADM_BASE, **cfg}), *cls_args), dict(norm_images=True, tile_stats_norms=True)
+
+
+def adm_block(dim, cls="ADMBaseBlock", **kw):
+    """A stand-alone block: no pool, every buffer torch's own ("fresh")."""
+    from diffsci_amd.models.nets import adm as nets
+    return getattr(nets, cls)(dimension=dim, **kw), {}
+
+
 class Net:
     """One case's network under trace: c.net, the recorder c.rec, named inputs from c.f / c.x."""
 
-    def __init__(self, rec, pool, dim=2, side=8, cls="PUNetG", cls_args=(), switches=(), **cfg):
-        from diffsci_amd.models.nets import punetg
-        from diffsci_amd.models.nets.punetg_config import PUNetGConfig
+    def __init__(self, rec, pool, family=punetg, dim=2, side=8, switches=(), **kw):
         self.rec, self.dim, self.side, self.k = rec, dim, side, 0
-        config = PUNetGConfig(**{**BASE, "dimension": dim, **cfg})
-        self.net = net = getattr(punetg, cls)(config, *cls_args).eval()
+        net, fixed = family(dim, **kw)
+        self.net = net = net.eval()
         tensors = list(net.named_parameters()) + list(net.named_buffers())
         for k, (name, t) in enumerate(tensors):
             with torch.no_grad():
                 t.copy_(pattern(k, *t.shape))
             rec.name(name, t.detach())
         self.k = len(tensors)
-        net.pool_route, net.norm_images = "epilogue", True                       # whatever the environment says
-        for name, v in switches:
+        for name, v in list(fixed.items()) + list(switches):
             setattr(net, name, v)
-        net._ws = pool
+        if hasattr(net, "_ws"):
+            net._ws = pool
         names = {id(m): n for n, m in net.named_modules()}
-        for key, v in net.packed_weights().items():
-            label = "pk:" + (names[key[0]] + "." + key[1] if isinstance(key, tuple) else names[key])
-            self._name_packed(label, v)
+        for key, v in (net.packed_weights() if hasattr(net, "packed_weights") else net._packs()).items():
+            label = key if isinstance(key, str) else (names[key[0]] + "." + key[1] if isinstance(key, tuple) else names[key])
+            self._name_packed("pk:" + label, v)
 
     def _name_packed(self, label, v):
         if isinstance(v, torch.Tensor):
@@ -144,7 +164,7 @@ class Net:
 
 
 def _forward(c):
-    """Fields: the whole eager evaluation, time embedding and per-block MLPs included.  Volumes: from tabulated shifts of known
+    """PUNetG fields and ADM: the whole eager evaluation, time embedding and per-block MLPs included.  Volumes: from tabulated shifts of known
     contents -- ops.conv3d_mfma copies the shift rows into a pool buffer with ATen, and the MLPs' results are never computed."""
     if c.dim == 2:
         c.net.forward_unguarded(c.x(), c.f("t", B))
@@ -225,11 +245,87 @@ CASES = {
 }
 
 
-def trace_of(name):
+def _adm_rows(c):
+    shifts = [c.f(f"shift{k}", 5, 2 * blk.cout) for k, blk in enumerate(c.net._blocks())]
+    c.net.forward_with_shifts(c.x(), shifts, row=3, out=c.x(c.net.config.output_channels, "out"))
+
+
+def _adm_cond(c):
+    c.net.forward_unguarded(c.x(), c.f("t", B), c.f("y", B, c.net.config.output_embed_dim))
+
+
+def _block(c):
+    """blk(x, te[, skip]) of a stand-alone block, on fields or volumes."""
+    blk, sides = c.net, [c.side] * c.dim
+    skip = c.f("skip", B, blk.channels_skip, *sides) if blk.channels_skip else None
+    blk(c.f("x", B, blk.channels_in, *sides), c.f("te", B, blk.channels_embed), skip)
+
+
+def acase(**kw):
+    return case(family=adm, **kw)
+
+
+def blocks(name, side=8, side3=4, **kw):
+    """One stand-alone block with a residual branch, on fields and on volumes."""
+    kw = dict(run=_block, family=adm_block, channels_in=16, channels_out=32, channels_embed=8, has_residual=True, **kw)
+    return {f"block_{name}_2d": case(side=side, **kw), f"block_{name}_3d": case(dim=3, side=side3, **kw)}
+
+
+IMAGES = dict(model_channels=32, side=16, switches=(("fuse_max_cot", 0),))
+ADM_CASES = {
+    "default": acase(),
+    "circular": acase(convolution_type="circular"),
+    "decoder2": acase(decoder_type=2),
+    "add": acase(skip_integration_type="add"),
+    "decoder2_add": acase(decoder_type=2, skip_integration_type="add"),
+    "factor3": acase(transition_scale_factor=3, side=12),
+    "factor1": acase(transition_scale_factor=1),
+    "norms_swapped": acase(first_resblock_norm="GroupRMS", second_resblock_norm="GroupLN"),
+    "unfused": acase(switches=(("fuse_norm", False),)),
+    "images": acase(**IMAGES),
+    "images_off": acase(**{**IMAGES, "switches": (("fuse_max_cot", 0), ("norm_images", False))}),
+    "images_stats_pass": acase(**{**IMAGES, "switches": (("fuse_max_cot", 0), ("tile_stats_norms", False))}),
+    "factor3_images": acase(**{**IMAGES, "side": 12}, transition_scale_factor=3),
+    "factor1_images": acase(**IMAGES, transition_scale_factor=1),
+    "bf16x6": acase(switches=(("conv_precision", "bf16x6"),)),
+    "fp32": acase(switches=(("conv_precision", "fp32"),)),
+    "exact_input": acase(switches=(("exact_input_layer", True),)),
+    "no_parity": acase(switches=(("upsample_parity", False),)),
+    "out8": acase(output_channels=8),
+    "two_levels": acase(channel_expansion=(2, 2), side=16),
+    "one_each": acase(number_resnet_downward_block=1, number_resnet_upward_block=1),
+    "attn1": acase(number_resnet_attn_block=1),
+    "no_attn_residual": acase(attn_residual=False),
+    "rows": acase(run=_adm_rows),
+    "side64_images": acase(model_channels=32, side=64, switches=(("fuse_max_cot", 0),)),          # ds_conv2d_h3_up_img
+    "side64_images_off": acase(side=64, switches=(("norm_images", False),)),                     # ds_conv2d_h3_up
+    "cond": acase(run=_adm_cond, cls_args=(Half(),)),
+    **blocks("plain"),
+    **blocks("down", image_sample="downsample"),
+    **blocks("up", image_sample="upsample"),
+    **blocks("down3", side3=6, image_sample="downsample", image_sample_factor=3, side=12),
+    **blocks("up3", image_sample="upsample", image_sample_factor=3),
+    **blocks("skip_concat", channels_skip=16),
+    **blocks("skip_add", channels_skip=16, skip_integration_type="add"),
+    **blocks("up_skip_concat", image_sample="upsample", channels_skip=16),
+    **blocks("attn", has_attn=True),
+    **blocks("attn_heads2", has_attn=True, attn_heads=2),
+    **blocks("attn_no_residual", has_attn=True, attn_residual=False),
+    **blocks("down_fp32", image_sample="downsample", switches=(("conv_precision", "fp32"),)),
+    **blocks("up_fp32", image_sample="upsample", switches=(("conv_precision", "fp32"),)),
+    "block_encoder_2d": case(run=_block, family=adm_block, cls="ADMEncoderBlock", channels_in=16, channels_out=32,
+                             channels_embed=8, has_downsample=True, has_residual=True),
+    "block_decoder_3d": case(run=_block, family=adm_block, cls="ADMDecoderBlock", dim=3, side=4, channels_in=16, channels_out=32,
+                             channels_embed=8, channels_skip=16, has_upsample=True, has_residual=True),
+}
+TABLES = {"net_trace": CASES, "adm_trace": ADM_CASES}                               # golden file -> its case table
+
+
+def trace_of(name, cases=CASES):
     """The pinned record of one case."""
     from diffsci_amd import ops
     N = _native()
-    run, pooled, kw = CASES[name]
+    run, pooled, kw = cases[name]
     rec = Recorder(N.lib(), pooled)
     pool = Pool(rec)
     saved = [(N, "lib", N.lib), (ops, "_stream", ops._stream), (ops, "_off_device", ops._off_device)]

@@ -38,8 +38,8 @@ for use_graph in (False, True, True, True):
 ops.conv3d_mfma = orig_mfma
 print("--- attention arena: skip (monkeypatch _AmaxArena.of to reduce into fresh rows is not possible under capture); instead disable attention amax")
 import diffsci_amd.models.nets.punetg as P
-oa = net._amax_kw
-net._amax_kw = lambda **kw: {"in_amax": ops.NORMALISED} if "in_amax" in kw else {}
+oa = P._amax_kw
+P._amax_kw = lambda pack, **kw: {"in_amax": ops.NORMALISED} if "in_amax" in kw else {}
 module._plans.clear()
 for use_graph in (False, True, True, True):
     module.use_graph = use_graph

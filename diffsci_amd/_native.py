@@ -151,6 +151,13 @@ _PROTOS = {
     "ds_si_inpaint_counters": (c_uint64, [c_int, c_size_t, c_int]),
     "ds_si_inpaint_step": (c_int, [_P, _P, _P, _P, _P, POINTER(EvalCoef), POINTER(SIStep), _P, _P, _P, _P, _P, _P, _P, c_uint64,
                                    c_int, c_size_t, _P, c_int]),
+    # ds_convit.hip: the flags word closes each list
+    "ds_channel_rmsnorm": (c_int, [_P, _P, _P, _P, c_int, c_int, c_int, c_int, c_int, c_int, c_float, _P, _P, c_int]),
+    "ds_rope2d": (c_int, [_P, _P, c_int, c_int, c_int, c_int, _P, _P, c_int]),
+    "ds_upsample_bilinear": (c_int, [_P, _P, c_int, c_int, c_int, c_int, _P, c_int]),
+    "ds_depthwise_conv_silu": (c_int, [_P, _P, _P, _P, c_int, c_int, c_int, c_int, c_int, _P, _P, c_int]),
+    "ds_swiglu": (c_int, [_P, _P, c_int, c_size_t, _P, _P, c_int]),
+    "ds_convit_blend": (c_int, [_P, _P, _P, _P, _P, c_size_t, _P, c_int]),
     "ds_graph_begin_capture": (c_int, [_P]),
     "ds_graph_end_capture": (c_int, [_P, POINTER(_P), POINTER(c_int)]),
     "ds_graph_launch": (c_int, [_P, _P]),

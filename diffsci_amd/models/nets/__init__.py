@@ -11,3 +11,4 @@ from . import autoencoderldm2d, autoencoderldm3d  # noqa: F401
 from .autoencoderldm3d import AttnBlock, AutoencoderKL, Decoder, ResnetBlock, Upsample, ddconfig  # noqa: F401
 from . import vaenet  # noqa: F401
 from .vaenet import VAENet, VAENetConfig  # noqa: F401
+from .convit import ConVit, ConVitBlock, ConVitConfig  # noqa: F401

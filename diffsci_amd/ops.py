@@ -1799,6 +1799,144 @@ def patch_unembed(x, w, bias, patch, shape, out=None):
     return out
 
 
+# ---------------------------------------------------------------- streaming layers of ConVit (ds_convit.hip)
+RMS_EPS = float(torch.finfo(torch.float32).eps)      # ChannelRMSNorm's eps (convit.py:237)
+RMS_FUSED_POOLS = (1, 2, 4)                           # pooling factors ds_channel_rmsnorm applies itself
+# Each wrapper below builds its argument tuple first and touches the library last, so every pointer and extent is checked
+# before N.lib() is called at all.
+
+
+def channel_rmsnorm(x, w, mod=None, row=None, pool=1, out=None, out_amax=None, eps=RMS_EPS, scratch=None):
+    """ChannelRMSNorm of x [B, E, H, W] plus an embedding row: out = x / sqrt(mean_c(x^2) + eps) * w [+ mod row], with mod
+    [rows, E]: 1 or B rows, or the single row `row` for the whole batch (the captured sampler's table).  pool=f writes
+    AvgPool2d(f) of that result, [B, E, H // f, W // f]; f in RMS_FUSED_POOLS is pooled inside the kernel, any other factor is the
+    unpooled result (in `scratch` [B, E, H, W] when given: captured code must not allocate) followed by avgpool_f.
+    out_amax: int32 [B] slots (zeroed) that receive the per-sample max |out| for an fp16x3 consumer.  out may not alias x."""
+    require_device(x, "x")
+    if x.dim() != 4:
+        raise ValueError(f"channel_rmsnorm: x must be [B, E, H, W]; got {tuple(x.shape)}")
+    B, E, H, W = x.shape
+    _entries(w, E, "channel_rmsnorm: weight must have E={} entries", E)
+    f = _factor(pool)
+    if f > min(H, W):
+        raise ValueError(f"channel_rmsnorm: pool={f} exceeds the field {H}x{W}")
+    if _overlap(out, x):
+        raise ValueError("channel_rmsnorm: out must be a tensor other than x")
+    out = _out(out, (B, E, H // f, W // f), x, "channel_rmsnorm: out has shape {}, expected {}")
+    pmod, stride = None, 0
+    if mod is not None:
+        first, stride = _mod_rows(mod, E, B, row, "mod")
+        if mod.shape[1] != E:
+            raise ValueError(f"channel_rmsnorm: mod must be [rows, {E}]; got {tuple(mod.shape)}")
+        pmod = mod.data_ptr() + 4 * first
+    fused = f in RMS_FUSED_POOLS
+    dst = out
+    if not fused:
+        if _overlap(scratch, x) or _overlap(scratch, out):
+            raise ValueError("channel_rmsnorm: scratch must be a tensor other than x and out")
+        dst = _out(scratch, (B, E, H, W), x, "channel_rmsnorm: scratch has shape {}, expected {}")
+    args = (_p(dst, "out" if fused else "scratch"), _p(x, "x"), _p(w, "weight"), pmod, stride, B, E, H, W, f if fused else 1, float(eps),
+            _pi(out_amax, B, "out_amax") if fused else None, _stream(), 0)
+    N.check(N.lib().ds_channel_rmsnorm(*args), "ds_channel_rmsnorm")
+    if not fused:
+        avgpool_f(dst, f, out=out)
+        if out_amax is not None:
+            absmax_rows(out, B, out=out_amax)
+    return out
+
+
+def rope2d(qkv, E, heads, cos_sin, out_amax=None):
+    """LearnedRoPE in place on the q and k thirds of qkv [B, 3E, L]: with d = E / heads, rows (h*d + 2i, h*d + 2i + 1) become
+    (a cos - b sin, a sin + b cos) with cos, sin = cos_sin[l, i] (cos_sin [L, d/2, 2]); the v third is left untouched.
+    out_amax: int32 [2, B] slots (zeroed) that receive max |q, k| after the rotation and max |v|: attention(in_amax=)."""
+    require_device(qkv, "qkv")
+    if qkv.dim() != 3 or qkv.shape[1] != 3 * E:
+        raise ValueError(f"rope2d: qkv must be [B, 3E, L] with E={E}; got {tuple(qkv.shape)}")
+    B, _, L = qkv.shape
+    heads = _check_heads(E, heads)
+    d = E // heads
+    if d % 2:
+        raise ValueError(f"rope2d: the head width E / heads = {d} must be even")
+    require_device(cos_sin, "cos_sin")
+    if tuple(cos_sin.shape) != (L, d // 2, 2):
+        raise ValueError(f"rope2d: cos_sin must be {(L, d // 2, 2)}; got {tuple(cos_sin.shape)}")
+    args = (_p(qkv, "qkv"), _p(cos_sin, "cos_sin"), B, E, heads, L, _pi(out_amax, 2 * B, "out_amax"), _stream(), 0)
+    N.check(N.lib().ds_rope2d(*args), "ds_rope2d")
+    return qkv
+
+
+def upsample_bilinear(x, factor, out=None):
+    """F.interpolate(x, scale_factor=factor, mode="bilinear", align_corners=False) of a field [B, C, H, W], any integer
+    factor >= 1."""
+    f = _factor(factor)
+    require_device(x, "x")
+    if x.dim() != 4:
+        raise ValueError(f"upsample_bilinear: x must be [B, C, H, W]; got {tuple(x.shape)}")
+    B, C, H, W = x.shape
+    if _overlap(out, x):
+        raise ValueError("upsample_bilinear: out must be a tensor other than x")
+    out = _out(out, (B, C, f * H, f * W), x, "upsample_bilinear: out has shape {}, expected {}")
+    args = (_p(out, "out"), _p(x, "x"), B * C, H, W, f, _stream(), 0)
+    N.check(N.lib().ds_upsample_bilinear(*args), "ds_upsample_bilinear")
+    return out
+
+
+DEPTHWISE_MAX_KERNEL = 7
+
+
+def depthwise_conv_silu(x, w, b, out=None, out_amax=None):
+    """SiLU(depthwise k x k 'same' zero-padded convolution + bias) of x [B, E, H, W]: w [E, 1, k, k] (k odd, at most
+    DEPTHWISE_MAX_KERNEL), b [E] or None.  out_amax: as channel_rmsnorm.  out may not alias x."""
+    require_device(x, "x")
+    if x.dim() != 4:
+        raise ValueError(f"depthwise_conv_silu: x must be [B, E, H, W]; got {tuple(x.shape)}")
+    B, E, H, W = x.shape
+    if w.dim() != 4 or w.shape[0] != E or w.shape[1] != 1 or w.shape[2] != w.shape[3]:
+        raise ValueError(f"depthwise_conv_silu: weight must be [{E}, 1, k, k]; got {tuple(w.shape)}")
+    k = w.shape[2]
+    if k % 2 == 0 or k > DEPTHWISE_MAX_KERNEL:
+        raise NotImplementedError(f"depthwise_conv_silu: kernel size {k}: odd sizes up to {DEPTHWISE_MAX_KERNEL} are implemented")
+    _entries(b, E, "depthwise_conv_silu: bias must have E={} entries", E)
+    if _overlap(out, x):
+        raise ValueError("depthwise_conv_silu: out must be a tensor other than x")
+    out = _out(out, (B, E, H, W), x, "depthwise_conv_silu: out has shape {}, expected {}")
+    args = (_p(out, "out"), _p(x, "x"), _p(w, "weight"), _p(b, "bias"), B, E, H, W, k,
+            _pi(out_amax, B, "out_amax"), _stream(), 0)
+    N.check(N.lib().ds_depthwise_conv_silu(*args), "ds_depthwise_conv_silu")
+    return out
+
+
+def swiglu(ag, out=None, out_amax=None):
+    """ag [B, 2C, ...] -> SiLU(ag[:, :C]) * ag[:, C:], [B, C, ...].  out_amax: as channel_rmsnorm.  out may not overlap ag."""
+    require_device(ag, "ag")
+    if ag.dim() < 2 or ag.shape[1] % 2:
+        raise ValueError(f"swiglu: ag must be [B, 2C, ...]; got {tuple(ag.shape)}")
+    B, C = ag.shape[0], ag.shape[1] // 2
+    if _overlap(out, ag):
+        raise ValueError("swiglu: out must not overlap ag")
+    out = _out(out, (B, C) + tuple(ag.shape[2:]), ag, "swiglu: out has shape {}, expected {}")
+    args = (_p(out, "out"), _p(ag, "ag"), B, out.numel() // max(B, 1), _pi(out_amax, B, "out_amax"), _stream(), 0)
+    N.check(N.lib().ds_swiglu(*args), "ds_swiglu")
+    return out
+
+
+def convit_blend(u, xc, x0, s, out=None):
+    """((1 - s) * u + s * xc) + x0, with s a one-element device tensor (read by the kernel: no host read, so the call can be
+    captured).  out may be x0 (in place), not u or xc."""
+    require_device(u, "u")
+    if tuple(xc.shape) != tuple(u.shape) or tuple(x0.shape) != tuple(u.shape):
+        raise ValueError(f"convit_blend: u, xc and x0 must have one shape; got {tuple(u.shape)}, {tuple(xc.shape)}, {tuple(x0.shape)}")
+    require_device(s, "s")
+    if s.numel() != 1:
+        raise ValueError(f"convit_blend: s must hold one element; got {tuple(s.shape)}")
+    if _overlap(out, u) or _overlap(out, xc) or (_overlap(out, x0) and out.data_ptr() != x0.data_ptr()):
+        raise ValueError("convit_blend: out may alias x0 only")
+    out = _out(out, tuple(u.shape), u, "convit_blend: out has shape {}, expected {}")
+    args = (_p(out, "out"), _p(u, "u"), _p(xc, "xc"), _p(x0, "x0"), _p(s, "s"), u.numel(), _stream(), 0)
+    N.check(N.lib().ds_convit_blend(*args), "ds_convit_blend")
+    return out
+
+
 def fourier_channels(x, W, out=None):
     """ConvolutionalFourierProjection: x [B, C, *spatial], W [C, D] -> [B, 2D, *spatial] = cat[sin, cos](x . 2*pi*W)."""
     require_device(x, "x")

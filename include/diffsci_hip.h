@@ -719,6 +719,43 @@ int ds_si_inpaint_step(float* x_out, float* xin_out, const float* x, const float
                        int B, size_t n_per_sample, void* stream, int flags);
 
 /* ------------------------------------------------------------------------------------
+ * Streaming layers of the ConVit score network (convit.py), ds_convit.hip.  Tensors are fp32
+ * [B, E, H, W]; the per-sample maxima (out_amax: optional int32 slots holding float bits,
+ * zeroed or merged into) serve the fp16x3 launch that reads the result.  No allocation, no
+ * synchronisation.  flags: 0 (none defined; the word closes each list as ds_conv2d_h3_pc's does).
+ * ---------------------------------------------------------------------------------- */
+
+/* ChannelRMSNorm + the block's embedding row (convit.py:236-243, 618, 633), then AvgPool2d(pool) (convit.py:619):
+ *   n[b,e,y,x] = x[b,e,y,x] / sqrt(mean_e(x[b,:,y,x]^2) + eps) * w[e] + mod[b*mod_stride + e]
+ *   out [B, E, H/pool, W/pool] = the mean of n over pool x pool pixels (floor output size); pool = 1: out = n.
+ * w and mod may be NULL (1 and 0).  x is read once: a pixel's channels stay in registers, E <= 1024.  pool: 1, 2 or 4
+ * (DS_ERR_UNSUPPORTED otherwise).  out may not alias x. */
+int ds_channel_rmsnorm(float* out, const float* x, const float* w, const float* mod, int mod_stride, int B, int E, int H, int W, int pool,
+                       float eps, unsigned* out_amax, void* stream, int flags);
+
+/* LearnedRoPE on the q and k thirds of qkv [B, 3E, L], in place (convit.py:369-388, 495-496): with d = E / heads (even), the rows
+ * (h*d + 2i, h*d + 2i + 1) of each of the two thirds become (a cos - b sin, a sin + b cos), cos = cos_sin[l, i, 0],
+ * sin = cos_sin[l, i, 1], cos_sin [L, d/2, 2].  The v third is only read.  out_amax (optional, int32 [2, B]): max |q, k| after the
+ * rotation and max |v| per sample: the pair ds_attention_h3* reads. */
+int ds_rope2d(float* qkv, const float* cos_sin, int B, int E, int heads, int L, unsigned* out_amax, void* stream, int flags);
+
+/* F.interpolate(scale_factor=factor, mode="bilinear", align_corners=False) of x [planes, H, W] -> out [planes, H*factor, W*factor],
+ * any integer factor >= 1: src = max((dst + 0.5) / factor - 0.5, 0), upper index clamped to the last. */
+int ds_upsample_bilinear(float* out, const float* x, int planes, int H, int W, int factor, void* stream, int flags);
+
+/* SiLU(depthwise ks x ks 'same' zero-padded convolution + bias) of x [B, E, H, W] (convit.py:626): w [E, 1, ks, ks], bias [E] or
+ * NULL, ks odd <= 7.  out may not alias x. */
+int ds_depthwise_conv_silu(float* out, const float* x, const float* w, const float* bias, int B, int E, int H, int W, int ks,
+                           unsigned* out_amax, void* stream, int flags);
+
+/* The SwiGLU gate (convit.py:327): ag [B, 2 * n_per_sample] -> out[b, j] = SiLU(ag[b, j]) * ag[b, n_per_sample + j]. */
+int ds_swiglu(float* out, const float* ag, int B, size_t n_per_sample, unsigned* out_amax, void* stream, int flags);
+
+/* The fusion blend and the residual (convit.py:629-631): out = ((1 - s) * u + s * xc) + x0 over n elements, s = *s_dev a device
+ * scalar (sigmoid(fusion_weight)).  out may alias x0. */
+int ds_convit_blend(float* out, const float* u, const float* xc, const float* x0, const float* s_dev, size_t n, void* stream, int flags);
+
+/* ------------------------------------------------------------------------------------
  * hipGraph capture of a launch sequence (the whole N-step loop is captured once per
  * (network, nsteps, batch) and replayed).
  * ---------------------------------------------------------------------------------- */

@@ -4,21 +4,14 @@
 // concatenated by PUNetGCond (punetg.py:719-735), an extra_residual module's output, slice copies of volumes.
 // HBM-bound: one read pass, 4 B/elt.
 #include "ds_common.h"
+#include "ds_stream.h"
 
 namespace {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
+using ds::amax4;
+using ds::f32x4;
+using ds::wave_commit_max_always;
 constexpr int NT = 256;
-
-__device__ __forceinline__ float abs_max4(f32x4 v) {
-  return fmaxf(fmaxf(__builtin_fabsf(v.x), __builtin_fabsf(v.y)), fmaxf(__builtin_fabsf(v.z), __builtin_fabsf(v.w)));
-}
-
-__device__ __forceinline__ void block_commit(unsigned* slot, float m) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o, 64));
-  if ((threadIdx.x & 63) == 0) atomicMax(slot, __builtin_bit_cast(unsigned, m));   // non-negative floats order like their bits
-}
 
 // grid (blocks per row, rows); fmaxf drops NaNs, so a row of NaNs reports 0 (the consuming kernel then runs unscaled
 // and the NaNs propagate through its arithmetic as they would anyway)
@@ -30,13 +23,12 @@ __global__ __launch_bounds__(NT) void k_absmax_rows(unsigned* __restrict__ out, 
     const f32x4* r4 = reinterpret_cast<const f32x4*>(row);
     const size_t n4 = n_per_row / 4;
     for (size_t i = (size_t)blockIdx.x * NT + threadIdx.x; i < n4; i += (size_t)gridDim.x * NT) {
-      const f32x4 v = r4[i];
-      m = fmaxf(m, fmaxf(fmaxf(__builtin_fabsf(v.x), __builtin_fabsf(v.y)), fmaxf(__builtin_fabsf(v.z), __builtin_fabsf(v.w))));
+      m = fmaxf(m, amax4(r4[i]));
     }
   } else {
     for (size_t i = (size_t)blockIdx.x * NT + threadIdx.x; i < n_per_row; i += (size_t)gridDim.x * NT) m = fmaxf(m, __builtin_fabsf(row[i]));
   }
-  block_commit(out + blockIdx.y, m);
+  wave_commit_max_always(out + blockIdx.y, m);
 }
 
 __global__ void k_fill_u32(unsigned* __restrict__ p, unsigned value, size_t n) {
@@ -107,9 +99,9 @@ __global__ __launch_bounds__(NTI) void k_input_amax(unsigned* __restrict__ arena
       size_t i = threadIdx.x;
       for (; i + 3 * NTI < n4; i += 4 * NTI) {
         const f32x4 t0 = r4[i], t1 = r4[i + NTI], t2 = r4[i + 2 * NTI], t3 = r4[i + 3 * NTI];
-        v = fmaxf(v, fmaxf(fmaxf(abs_max4(t0), abs_max4(t1)), fmaxf(abs_max4(t2), abs_max4(t3))));
+        v = fmaxf(v, fmaxf(fmaxf(amax4(t0), amax4(t1)), fmaxf(amax4(t2), amax4(t3))));
       }
-      for (; i < n4; i += NTI) v = fmaxf(v, abs_max4(r4[i]));
+      for (; i < n4; i += NTI) v = fmaxf(v, amax4(r4[i]));
     } else {
       for (size_t i = threadIdx.x; i < HW; i += NTI) v = fmaxf(v, __builtin_fabsf(row[i]));
     }

@@ -17,11 +17,12 @@
 // LDS one tile ahead.  Q^T (E/2 registers), O^T (E/2 registers) and S^T (16) live in the unified
 // 512-entry register file (one wave per SIMD).
 #include "ds_common.h"
+#include "ds_stream.h"
 
 namespace {
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));   // native vector: HIP's float4 struct defeats SROA here
+using ds::f32x4;
 constexpr int NT = 256;
 constexpr int KB = 32;       // keys per tile
 constexpr int VSTR = KB + 1; // padded V^T row

@@ -35,38 +35,25 @@
 
 #include "ds_common.h"
 #include "ds_conv_epilogue.h"
+#include "ds_h3_common.h"
 
 namespace {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
+using ds::f32x4;
+using ds::wave_max;
+using ds_epi::f32x16;
+using ds_h3::f16x8;
+using ds_h3::split2;
+using ds_h3::u32x4;
 typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
 
 constexpr int NT = 256;
 constexpr int KB = 32;       // keys per tile
 constexpr float RESCALE_T = 8.0f;
 
-// Exact-sum split of two fp32 values into packed fp16 hi / lo pairs.  The low piece MUST be the
-// remainder against the very same rounded high piece that is stored: hipcc otherwise rounds the
-// stored pair with v_cvt_pk_f16_f32 and the remainder's reference with v_cvt_f16_f32, and the two
-// disagree on exact ties (measured on gfx950: hi + lo off by one fp16 ulp, 2^-11 relative, for one
-// value in ~8000).  Deriving the reference from the packed bits removes the second rounding.
 // e^x for the softmax numerators (x <= RESCALE_T): one FMA and the hardware exp2 (1 ulp; the argument's rounding adds
 // |x| * 2^-24 relative, i.e. < 1e-6 wherever the result is not negligible) instead of libm's range-reduced expf
 constexpr float LOG2E = 1.44269504088896341f;
-
-__device__ __forceinline__ void split2(float a, float b, unsigned& hi, unsigned& lo) {
-  f16x2 h = {(_Float16)a, (_Float16)b};
-  unsigned hp = __builtin_bit_cast(unsigned, h);
-  asm volatile("" : "+v"(hp));                       // opaque: both uses below see these exact bits
-  const f16x2 hq = __builtin_bit_cast(f16x2, hp);
-  f16x2 l = {(_Float16)(a - (float)hq[0]), (_Float16)(b - (float)hq[1])};
-  hi = hp;
-  lo = __builtin_bit_cast(unsigned, l);
-}
 
 __device__ __forceinline__ f16x8 as_f16x8(u32x4 v) { return __builtin_bit_cast(f16x8, v); }
 
@@ -466,7 +453,7 @@ __global__ __launch_bounds__(NT) void k_attn3h(float* out, const float* __restri
         amax = fmaxf(amax, __builtin_fabsf(o));
       }
   }
-  if (out_amax) ds_epi::commit_amax(out_amax + b, amax);
+  if (out_amax) ds::wave_commit_max_always(out_amax + b, amax);
 }
 
 // Pre-pass of the IMG form: one workgroup per (key tile, sample) writes the tile's K and V images
@@ -590,7 +577,7 @@ __global__ __launch_bounds__(64) void k_attn_heads_generic(float* out, const flo
     ps[k] = sc;
     mx = fmaxf(mx, sc);
   }
-  for (int o = 32; o > 0; o >>= 1) mx = fmaxf(mx, __shfl_xor(mx, o, 64));
+  mx = wave_max(mx);
   float sum = 0.f;
   for (int k = lane; k < L; k += 64) {
     const float p = expf(ps[k] - mx);

@@ -18,11 +18,12 @@
 // (UpSampler); the epilogue applies bias, the per-(sample,channel) time shift and up to two
 // residual tensors, so none of these is a separate pass over HBM.
 #include "ds_common.h"
+#include "ds_stream.h"
 
 namespace {
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
+using ds::f32x4;
 
 constexpr int TH = 8;     // tile rows
 constexpr int TW = 32;    // tile columns (= MFMA N)

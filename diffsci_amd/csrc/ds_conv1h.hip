@@ -14,13 +14,14 @@
 //   blockIdx -> tile is XCD-aware: the Cout/64 workgroups sharing an input tile run on one XCD.
 #include "ds_common.h"
 #include "ds_conv_epilogue.h"
+#include "ds_h3_common.h"
 
 namespace {
 
 using ds_epi::f32x16;
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
+using ds_h3::f16x8;
+using ds_h3::split2;
+using ds_h3::u32x4;
 typedef const __attribute__((address_space(1))) float* gfloat_ptr;
 typedef const __attribute__((address_space(1))) char* gchar_ptr;
 typedef float f32x2 __attribute__((ext_vector_type(2)));
@@ -66,17 +67,6 @@ struct Conv1hArgs {
   int n_cot_wg;           // workgroups per pixel tile: n_cot, or n_cot / 2 with two channel tiles per workgroup
   unsigned n_blocks;
 };
-
-// see ds_conv3h.hip: the remainder must be taken against the stored (packed-converted) high piece
-__device__ __forceinline__ void split2(float a, float b, unsigned& hi, unsigned& lo) {
-  f16x2 h = {(_Float16)a, (_Float16)b};
-  unsigned hp = __builtin_bit_cast(unsigned, h);
-  asm volatile("" : "+v"(hp));                       // opaque: both uses below see these exact bits
-  const f16x2 hq = __builtin_bit_cast(f16x2, hp);
-  f16x2 l = {(_Float16)(a - (float)hq[0]), (_Float16)(b - (float)hq[1])};
-  hi = hp;
-  lo = __builtin_bit_cast(unsigned, l);
-}
 
 __device__ __forceinline__ void step_barrier() {
   // LDS writes of this wave are done (lgkmcnt); outstanding global loads are NOT waited for

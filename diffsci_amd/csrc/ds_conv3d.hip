@@ -10,6 +10,7 @@
 // thread then reads its 27 taps once per channel and reuses each across the 16 output channels (weights come
 // as 16-byte broadcast reads).
 #include "ds_common.h"
+#include "ds_stream.h"
 
 namespace {
 
@@ -293,7 +294,7 @@ __global__ __launch_bounds__(256) void k_from_slices_stats(float* y, const float
     if (r2) v0 = v0 + r2[o + i0];
   }
   float ks = v0;
-  for (int k = 32; k > 0; k >>= 1) ks += __shfl_xor(ks, k, 64);
+  ks = ds::wave_sum(ks);
   if ((threadIdx.x & 63) == 0) kred[threadIdx.x >> 6] = ks;
   __syncthreads();
   const size_t kcount = first < HW ? (HW - first < 256 ? HW - first : 256) : 0;

@@ -8,7 +8,7 @@
 namespace ds_conv3 {
 
 using ds_epi::f32x16;
-using ds_epi::f32x4;
+using ds::f32x4;
 using ds_h3::u32x4;
 using ds_h3::f16x8;
 using ds_h3::split2;

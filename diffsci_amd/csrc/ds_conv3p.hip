@@ -646,7 +646,7 @@ __global__ __launch_bounds__(512, 2) void k_conv3p(const Conv3hArgs a) {
     }
     if (want_amax) {
 #pragma unroll
-      for (int k = 0; k < BK; ++k) s_amax = fmaxf(s_amax, ds_epi::abs_max4(v[k]));
+      for (int k = 0; k < BK; ++k) s_amax = fmaxf(s_amax, ds::amax4(v[k]));
     }
     if (stats) {
       f32x4 o[BK];
@@ -667,7 +667,7 @@ __global__ __launch_bounds__(512, 2) void k_conv3p(const Conv3hArgs a) {
     }
     return POOL ? BK + BK / 2 : BK;
   };
-  auto commit_amax_asm = [&]() __attribute__((always_inline)) {        // ds_epi::commit_amax with the atomic as assembly
+  auto commit_max = [&]() __attribute__((always_inline)) {             // ds::wave_commit_max_always, written out: see DESIGN 4.20
     float m = s_amax;
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o, 64));
@@ -854,7 +854,7 @@ __global__ __launch_bounds__(512, 2) void k_conv3p(const Conv3hArgs a) {
         }
         PSTAMP_FINE(6);
         if (head) { young += store_batch(RB, 1); young += res_prefetch(RA, 2); }
-        if (second) { young += store_batch(RB, 3); if (want_amax) commit_amax_asm(); }
+        if (second) { young += store_batch(RB, 3); if (want_amax) commit_max(); }
       }
       if (stamp < 48) PSTAMP(stamp);
       ++stamp;
@@ -951,7 +951,7 @@ __global__ __launch_bounds__(512, 2) void k_conv3p(const Conv3hArgs a) {
       store_batch(RA, 2);
       res_prefetch(RB, 3);
       store_batch(RB, 3);
-      if (want_amax) commit_amax_asm();
+      if (want_amax) commit_max();
     }
     bar_counted(0);
     if constexpr (!CONS) {

@@ -24,12 +24,14 @@
 // input global -> registers -> LDS because it is split on the way);
 // the fp32 -> 3 x bf16 split of the input happens once per staged element, in registers.
 #include "ds_common.h"
+#include "ds_h3_common.h"
+#include "ds_stream.h"
 
 namespace {
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
+using ds::f32x4;
+using ds_h3::u32x4;
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 
 constexpr int TH = 8, TW = 32, COT = 64, NT = 256;

@@ -6,14 +6,18 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include "ds_stream.h"
+
 #ifndef DS_AMAX_EPILOGUE
 #define DS_AMAX_EPILOGUE 1      // 0: measurement builds only (tools/ab_bench.sh): what does the out_amax code cost the launches that do not use it?
 #endif
 
 namespace ds_epi {
 
+using ds::amax4;
+using ds::f32x4;
+using ds::wave_commit_max_always;
 typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 struct Args {
   float* out;
@@ -97,16 +101,6 @@ __device__ __forceinline__ ActScale act_scale_of(unsigned bits, int wshift) {
   s.unscale = __builtin_bit_cast(float, (unsigned)(127 - wshift - k) << 23);
   s.inv_scale = __builtin_bit_cast(float, (unsigned)(127 - k) << 23);
   return s;
-}
-
-// wave-wide maximum of non-negative values, merged into the sample's slot
-__device__ __forceinline__ void commit_amax(unsigned* slot, float m) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o, 64));
-  if ((threadIdx.x & 63) == 0) atomicMax(slot, __builtin_bit_cast(unsigned, m));
-}
-__device__ __forceinline__ float abs_max4(f32x4 v) {
-  return fmaxf(fmaxf(__builtin_fabsf(v.x), __builtin_fabsf(v.y)), fmaxf(__builtin_fabsf(v.z), __builtin_fabsf(v.w)));
 }
 
 // sum over the 8 lanes of an aligned lane octet, then over the pair of octets of a 16-lane row
@@ -305,7 +299,7 @@ __device__ __forceinline__ void store_tile_rows(float* tile, const Args& e, cons
         if (ok[k]) *reinterpret_cast<f32x4*>(e.out + idx[k]) = v[k];
       if (want_amax) {
 #pragma unroll
-        for (int k = 0; k < 4; ++k) amax = ok[k] ? fmaxf(amax, abs_max4(v[k])) : amax;
+        for (int k = 0; k < 4; ++k) amax = ok[k] ? fmaxf(amax, amax4(v[k])) : amax;
       }
       if (stats) {
 #pragma unroll
@@ -323,7 +317,7 @@ __device__ __forceinline__ void store_tile_rows(float* tile, const Args& e, cons
         }
       }
     }
-    if (want_amax) commit_amax(e.out_amax, amax);
+    if (want_amax) wave_commit_max_always(e.out_amax, amax);
     if (stats) {                                      // all reads of the wave's tile are done: reuse its head as [32*MT co][4]
       if ((lane & 15) == 0) {
 #pragma unroll
@@ -361,7 +355,7 @@ __device__ __forceinline__ void store_tile_rows(float* tile, const Args& e, cons
         if (lane == 0) { tile[4 * co] = K; tile[4 * co + 1] = sv; tile[4 * co + 2] = qv; tile[4 * co + 3] = nv; }
       }
     }
-    if (DS_AMAX_EPILOGUE && e.out_amax) commit_amax(e.out_amax, amax);
+    if (DS_AMAX_EPILOGUE && e.out_amax) wave_commit_max_always(e.out_amax, amax);
   }
 }
 

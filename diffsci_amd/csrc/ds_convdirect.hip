@@ -6,11 +6,12 @@
 //   8 input channels at a time are staged as zero- (or periodically) padded 18 x 66 patches in LDS;
 //   weights are wave-uniform scalar loads (constant address space).
 #include "ds_common.h"
+#include "ds_stream.h"
 #include <cstdlib>
 
 namespace {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
+using ds::f32x4;
 typedef float f32x2 __attribute__((ext_vector_type(2)));
 constexpr int NT = 256, TH = 16, TW = 64, KCH = 8;
 constexpr int PH = TH + 2, PSTR = 68;                   // row stride padded to a multiple of 4 floats

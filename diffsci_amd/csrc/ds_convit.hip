@@ -6,8 +6,9 @@
 // Streaming kernels: one read and one write of the tensor, no matrix cores.  Arithmetic is one rounding per operation
 // (-ffp-contract=off); the depthwise taps are an fmaf chain in (dy, dx) order.  Kernels whose result feeds an fp16x3 launch merge
 // the per-sample max |out| into zeroed int32 slots (float bits), the convention of ds_conv_epilogue.h, through
-// ds::wave_commit_max (ds_stream.h), which skips the atomic when the slot already covers the wave's maximum: an unconditional
-// atomicMax per wave on the sample's one address serialises in L2 and bounded every one of these kernels.
+// ds::wave_commit_max_if_greater (ds_stream.h), which skips the atomic when the slot already covers the wave's maximum: an
+// unconditional atomicMax per wave on the sample's one address serialises in L2 and bounded every one of these kernels
+// (DESIGN 4.19).
 //
 // Every entry point closes its argument list with a flags word after the stream (none are defined: pass 0).
 #include "ds_common.h"
@@ -18,7 +19,7 @@ namespace {
 using ds::amax4;
 using ds::f32x4;
 using ds::silu;
-using ds::wave_commit_max;
+using ds::wave_commit_max_if_greater;
 constexpr int NT = 256;
 
 bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
@@ -128,7 +129,7 @@ __global__ __launch_bounds__(NT) void k_channel_rms(float* __restrict__ out, con
       }
     }
   }
-  if (out_amax) wave_commit_max(out_amax + b, amax);
+  if (out_amax) wave_commit_max_if_greater(out_amax + b, amax);
 }
 
 template <int VEC>
@@ -208,8 +209,8 @@ __global__ __launch_bounds__(NT) void k_rope2d(float* qkv, const float* __restri
     }
   }
   if (out_amax) {                                       // merged maxima: a wave that saw no row of a kind commits 0
-    wave_commit_max(out_amax + b, mqk);
-    wave_commit_max(out_amax + B + b, mv);
+    wave_commit_max_if_greater(out_amax + b, mqk);
+    wave_commit_max_if_greater(out_amax + B + b, mv);
   }
 }
 
@@ -297,7 +298,7 @@ __global__ __launch_bounds__(NT) void k_depthwise_silu(float* __restrict__ out, 
     out[(size_t)plane * H * W + (size_t)oy * W + ox] = v;
     m = __builtin_fabsf(v);
   }
-  if (out_amax) wave_commit_max(out_amax + b, m);
+  if (out_amax) wave_commit_max_if_greater(out_amax + b, m);
 }
 
 // ---- SwiGLU gate: out[b, j] = SiLU(ag[b, j]) * ag[b, n + j], j < n = C * spatial (ag [B, 2C, ...]) ---------------------------------------
@@ -321,7 +322,7 @@ __global__ __launch_bounds__(NT) void k_swiglu(float* __restrict__ out, const fl
       o[i] = v;
     }
   }
-  if (out_amax) wave_commit_max(out_amax + blockIdx.y, m);
+  if (out_amax) wave_commit_max_if_greater(out_amax + blockIdx.y, m);
 }
 
 // ---- fusion blend: out = ((1 - s) * u + s * xc) + x0, s a device scalar (convit.py:629-631) ------------------------------------------------

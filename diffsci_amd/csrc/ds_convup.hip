@@ -29,7 +29,7 @@
 namespace {
 
 using ds_epi::f32x16;
-using ds_epi::f32x4;
+using ds::f32x4;
 using ds_h3::u32x4;
 using ds_h3::f16x8;
 using ds_h3::split2;
@@ -166,7 +166,7 @@ __device__ __forceinline__ void store_half_rows(int m, const float* tile, float*
     }
     if (e.res2) v = v + *reinterpret_cast<const f32x4*>(e.res2 + idx);
     if (ok) *reinterpret_cast<f32x4*>(e.out + idx) = v;
-    if (e.out_amax) amax = ok ? fmaxf(amax, ds_epi::abs_max4(v)) : amax;
+    if (e.out_amax) amax = ok ? fmaxf(amax, ds::amax4(v)) : amax;
     if (stats) {
       // lanes 0-15 / 16-31 of a 32-lane half hold rows r = 0 / 1 of one channel; the shift K is the channel's first value
       const float K = __shfl(ok ? v.x : 0.f, lane & 32, 64);
@@ -183,7 +183,7 @@ __device__ __forceinline__ void store_half_rows(int m, const float* tile, float*
       }
     }
   }
-  if (e.out_amax) ds_epi::commit_amax(e.out_amax, amax);
+  if (e.out_amax) ds::wave_commit_max_always(e.out_amax, amax);
 }
 
 // IMGIN: the low-resolution input arrives as pre-split fp16 hi / lo images (ds_gnorm1_apply_images / ds_inorm_silu_images:

@@ -11,17 +11,18 @@
 //     followed, when pool = 1, by the block's 2x2 average pooling (adm.py:316-319, 345-347).
 //   ds_gnorm1_apply_poolf  the same followed by an f x f average pooling, any f >= 1 (image_sample_factor != 2).
 #include "ds_common.h"
+#include "ds_h3_common.h"
+#include "ds_stream.h"
 
 namespace {
 
+using ds::silu;
+using ds::wave_sum;
+using ds_h3::image_plane;
+using ds_h3::split8;
+using ds_h3::u32x4;
 constexpr int NT = 256;
 constexpr int MAXCH = 256;   // phase-1 chunks per sample
-
-__device__ __forceinline__ double wave_sum_d(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
 
 __global__ __launch_bounds__(NT) void k_g1_partial(double* part, const float* __restrict__ x, size_t n_per_sample,
                                                    int chunks) {
@@ -54,8 +55,8 @@ __global__ __launch_bounds__(NT) void k_g1_partial(double* part, const float* __
       q += (double)v * (double)v;
     }
   }
-  s = wave_sum_d(s);
-  q = wave_sum_d(q);
+  s = wave_sum(s);
+  q = wave_sum(q);
   const int wid = threadIdx.x >> 6;
   if ((threadIdx.x & 63) == 0) { red[0][wid] = s; red[1][wid] = q; }
   __syncthreads();
@@ -74,8 +75,8 @@ __global__ void k_g1_final(float* stats, const double* __restrict__ part, int ch
     s += part[((size_t)b * chunks + i) * 2 + 0];
     q += part[((size_t)b * chunks + i) * 2 + 1];
   }
-  s = wave_sum_d(s);
-  q = wave_sum_d(q);
+  s = wave_sum(s);
+  q = wave_sum(q);
   if (threadIdx.x == 0) {
     if (kind == 0) {
       const double mean = s * inv_n;
@@ -89,8 +90,6 @@ __global__ void k_g1_final(float* stats, const double* __restrict__ part, int ch
     }
   }
 }
-
-__device__ __forceinline__ float silu(float v) { return v / (1.0f + expf(-v)); }
 
 // KIND 0: GroupNorm(1, C), stats = (mean, rstd); KIND 1: GroupRMSNorm(1, C), stats = (0, rms denominator);
 // either may be followed by FiLM (the second norm of an ADM block, adm.py:306-307,331-333); KIND 2: copy
@@ -201,20 +200,8 @@ __global__ __launch_bounds__(NT) void k_g1_apply_poolf(float* out, const float* 
 // k_g1_apply with the result written as the consuming convolution's pre-split fp16 hi / lo images (ds_conv2d_h3_img; layout and
 // rationale: ds_norm.hip, k_inorm_images).  One thread = one position of the padded image of one 8-channel group: border
 // positions store zeros, the others apply the same arithmetic as k_g1_apply (bit-identical values) to their 8 channels and split.
-typedef _Float16 g1_f16x2 __attribute__((ext_vector_type(2)));
-typedef unsigned g1_u32x4 __attribute__((ext_vector_type(4)));
-__device__ __forceinline__ void g1_split2(float a, float b, unsigned& hi, unsigned& lo) {        // ds_h3_common.h's split2
-  g1_f16x2 h = {(_Float16)a, (_Float16)b};
-  unsigned hp = __builtin_bit_cast(unsigned, h);
-  asm volatile("" : "+v"(hp));
-  const g1_f16x2 hq = __builtin_bit_cast(g1_f16x2, hp);
-  g1_f16x2 l = {(_Float16)(a - (float)hq[0]), (_Float16)(b - (float)hq[1])};
-  hi = hp;
-  lo = __builtin_bit_cast(unsigned, l);
-}
-
 template <int KIND, int POOL>
-__global__ __launch_bounds__(NT) void k_g1_apply_images(g1_u32x4* __restrict__ img, const float* __restrict__ x,
+__global__ __launch_bounds__(NT) void k_g1_apply_images(u32x4* __restrict__ img, const float* __restrict__ x,
                                                         const float* __restrict__ stats, const float* __restrict__ w,
                                                         const float* __restrict__ bias, const float* __restrict__ film1,
                                                         const float* __restrict__ film2, int film_stride, int C, int nchunk,
@@ -228,10 +215,10 @@ __global__ __launch_bounds__(NT) void k_g1_apply_images(g1_u32x4* __restrict__ i
   const int h = (int)(t & 1); t >>= 1;
   const int chunk = (int)(t % nchunk);
   const int b = (int)(t / nchunk);
-  g1_u32x4* hi_img = img + ((((size_t)b * nchunk + chunk) * 2 + 0) * 2 + h) * Hp * Wp;
-  g1_u32x4* lo_img = img + ((((size_t)b * nchunk + chunk) * 2 + 1) * 2 + h) * Hp * Wp;
+  u32x4* hi_img = image_plane(img, b, nchunk, chunk, 0, h, Hp, Wp);
+  u32x4* lo_img = image_plane(img, b, nchunk, chunk, 1, h, Hp, Wp);
   const size_t o = (size_t)py * Wp + px;
-  g1_u32x4 qh = {0u, 0u, 0u, 0u}, ql = {0u, 0u, 0u, 0u};
+  u32x4 qh = {0u, 0u, 0u, 0u}, ql = {0u, 0u, 0u, 0u};
   if (py >= 1 && py <= Ho && px >= 1 && px <= Wo) {
     const int y = py - 1, xq = px - 1;
     const float mean = stats[2 * b], sd = stats[2 * b + 1];
@@ -257,12 +244,7 @@ __global__ __launch_bounds__(NT) void k_g1_apply_images(g1_u32x4* __restrict__ i
         a[k] = 0.f;
       }
     }
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      unsigned ph, pl;
-      g1_split2(a[2 * j], a[2 * j + 1], ph, pl);
-      qh[j] = ph; ql[j] = pl;
-    }
+    split8([=](int k) { return a[k]; }, qh, ql);       // a by value: a reference capture compiles to other code
   }
   hi_img[o] = qh;
   lo_img[o] = ql;
@@ -270,7 +252,7 @@ __global__ __launch_bounds__(NT) void k_g1_apply_images(g1_u32x4* __restrict__ i
 
 // The fused loader's activation SiLU((x - M) * A + C) from a norm table [B, ceil16(C), 4] (ds_inorm_table / ds_gnorm1_table),
 // written as pre-split images: any plane size, any norm the tables describe.  Same arithmetic as the loader (hardware exp2 / rcp).
-__global__ __launch_bounds__(NT) void k_table_apply_images(g1_u32x4* __restrict__ img, const float* __restrict__ x,
+__global__ __launch_bounds__(NT) void k_table_apply_images(u32x4* __restrict__ img, const float* __restrict__ x,
                                                            const float4* __restrict__ table, int C, int nchunk, int H, int W,
                                                            size_t total) {
   const size_t i = (size_t)blockIdx.x * NT + threadIdx.x;
@@ -282,10 +264,10 @@ __global__ __launch_bounds__(NT) void k_table_apply_images(g1_u32x4* __restrict_
   const int h = (int)(t & 1); t >>= 1;
   const int chunk = (int)(t % nchunk);
   const int b = (int)(t / nchunk);
-  g1_u32x4* hi_img = img + ((((size_t)b * nchunk + chunk) * 2 + 0) * 2 + h) * Hp * Wp;
-  g1_u32x4* lo_img = img + ((((size_t)b * nchunk + chunk) * 2 + 1) * 2 + h) * Hp * Wp;
+  u32x4* hi_img = image_plane(img, b, nchunk, chunk, 0, h, Hp, Wp);
+  u32x4* lo_img = image_plane(img, b, nchunk, chunk, 1, h, Hp, Wp);
   const size_t o = (size_t)py * Wp + px;
-  g1_u32x4 qh = {0u, 0u, 0u, 0u}, ql = {0u, 0u, 0u, 0u};
+  u32x4 qh = {0u, 0u, 0u, 0u}, ql = {0u, 0u, 0u, 0u};
   if (py >= 1 && py <= H && px >= 1 && px <= W) {
     const float4* trow = table + ((size_t)b * nchunk + chunk) * 16 + 8 * h;
     float a[8];
@@ -295,17 +277,12 @@ __global__ __launch_bounds__(NT) void k_table_apply_images(g1_u32x4* __restrict_
       if (c < C) {
         const float4 p = trow[k];
         const float v = (x[(((size_t)b * C + c) * H + (py - 1)) * W + (px - 1)] - p.x) * p.y + p.z;
-        a[k] = v * __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(v * -1.44269504088896341f));     // ds_h3::fast_silu
+        a[k] = ds_h3::fast_silu(v);
       } else {
         a[k] = 0.f;
       }
     }
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      unsigned ph, pl;
-      g1_split2(a[2 * j], a[2 * j + 1], ph, pl);
-      qh[j] = ph; ql[j] = pl;
-    }
+    split8([=](int k) { return a[k]; }, qh, ql);
   }
   hi_img[o] = qh;
   lo_img[o] = ql;
@@ -431,7 +408,7 @@ int ds_gnorm1_apply_images(void* images, const float* x, const float* stats, con
   const int nchunk = (C + 15) / 16;
   const size_t total = (size_t)B * nchunk * 2 * (Ho + 2) * (Wo + 2);
   DS_REQUIRE((total + NT - 1) / NT < (1ull << 31), DS_ERR_SHAPE, "ds_gnorm1_apply_images: too many positions");
-  g1_u32x4* img = reinterpret_cast<g1_u32x4*>(images);
+  u32x4* img = reinterpret_cast<u32x4*>(images);
   dim3 g((unsigned)((total + NT - 1) / NT)), t(NT);
   hipStream_t s = ds::as_stream(stream);
 #define L(K, P) hipLaunchKernelGGL((k_g1_apply_images<K, P>), g, t, 0, s, img, x, stats, w, b, film_scale, film_shift, film_stride, C, nchunk, Ho, Wo, total)
@@ -452,7 +429,7 @@ int ds_table_apply_images(void* images, const float* x, const float* table, int 
   const size_t total = (size_t)B * nchunk * 2 * (H + 2) * (W + 2);
   DS_REQUIRE((total + NT - 1) / NT < (1ull << 31), DS_ERR_SHAPE, "ds_table_apply_images: too many positions");
   hipLaunchKernelGGL(k_table_apply_images, dim3((unsigned)((total + NT - 1) / NT)), dim3(NT), 0, ds::as_stream(stream),
-                     reinterpret_cast<g1_u32x4*>(images), x, reinterpret_cast<const float4*>(table), C, nchunk, H, W, total);
+                     reinterpret_cast<u32x4*>(images), x, reinterpret_cast<const float4*>(table), C, nchunk, H, W, total);
   DS_CHECK_LAUNCH("ds_table_apply_images");
   return DS_OK;
 }

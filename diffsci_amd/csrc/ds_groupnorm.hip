@@ -9,20 +9,21 @@
 // Sums are fp64 in a fixed order (thread-strided terms, a butterfly over the wave, the waves through LDS in index order):
 // results are reproducible bit for bit.  Arithmetic is one rounding per operation (-ffp-contract=off).
 #include "ds_normtab_common.h"
+#include "ds_stream.h"
 
 namespace {
 
+using ds::amax4;
+using ds::f32x4;
+using ds::silu;
+using ds::wave_max;
 using ds_nt::acc_tile;
 using ds_nt::group_sum_d;
 using ds_nt::inv_scale_of;
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 constexpr int NT = 256;
 constexpr int MAX_CHUNKS = 64;       // workgroups per channel row: the rest of a plane is grid-strided
 constexpr int TT = 1024;             // table kernel: one workgroup per sample
 constexpr int MAXG = 1024;
-
-__device__ __forceinline__ float silu(float v) { return v / (1.0f + expf(-v)); }
 
 template <int ACT>
 __device__ __forceinline__ float apply1(float x, float mean, float rstd, float w, float b) {
@@ -50,7 +51,7 @@ __global__ __launch_bounds__(NT) void k_gn_apply(float* __restrict__ out, const 
       f32x4 v = *reinterpret_cast<const f32x4*>(src + (size_t)i * 4);
       v.x = apply1<ACT>(v.x, mean, rstd, wc, bc); v.y = apply1<ACT>(v.y, mean, rstd, wc, bc);
       v.z = apply1<ACT>(v.z, mean, rstd, wc, bc); v.w = apply1<ACT>(v.w, mean, rstd, wc, bc);
-      m = fmaxf(m, fmaxf(fmaxf(__builtin_fabsf(v.x), __builtin_fabsf(v.y)), fmaxf(__builtin_fabsf(v.z), __builtin_fabsf(v.w))));
+      m = fmaxf(m, amax4(v));
       *reinterpret_cast<f32x4*>(dst + (size_t)i * 4) = v;
     } else {
       const float v = apply1<ACT>(src[i], mean, rstd, wc, bc);
@@ -145,7 +146,7 @@ __global__ __launch_bounds__(TT) void k_gn_table(float* __restrict__ table, cons
     }
     rows[c] = o;
   }
-  for (int o = 32; o > 0; o >>= 1) U = fmaxf(U, __shfl_xor(U, o, 64));
+  U = wave_max(U);
   if ((threadIdx.x & 63) == 0 && U > 0.f) atomicMax(&smax, __builtin_bit_cast(unsigned, U));    // LDS
   __syncthreads();
   const float inv = inv_scale_of(__builtin_bit_cast(float, smax));

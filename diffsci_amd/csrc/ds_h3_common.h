@@ -1,4 +1,6 @@
-// Pieces shared by the fp16x3 3x3 convolution kernels (ds_conv3h.hip, ds_convup.hip).
+// Pieces of the fp16x3 arithmetic, for every file that splits fp32 into fp16 hi / lo pairs: the packed vector types, the exact-sum
+// split, the fused loaders' SiLU, and the writers' side of the pre-split image layout.  (The one-read-one-write helpers and the
+// maximum commits are in ds_stream.h.)
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -37,6 +39,23 @@ __device__ __forceinline__ float fast_silu(float v) {
 __device__ __forceinline__ float fast_silu_scaled(float v, float inv_scale) {
   const float e = __builtin_amdgcn_exp2f(v * -1.44269504088896341f);
   return v * __builtin_amdgcn_rcpf(__builtin_fmaf(e, inv_scale, inv_scale));
+}
+
+// ---- pre-split images: the writers' side ---------------------------------------------------------------------------------------
+// images [B][chunk][piece 2][half 2][H+2][W+2] vectors of 8 channels (c = 16 chunk + 8 half + 0..7; piece 0 = hi, 1 = lo), zero
+// border, zero channels past C (rationale: ds_norm.hip, k_inorm_images).  Hp = H + 2, Wp = W + 2.
+__device__ __forceinline__ u32x4* image_plane(u32x4* img, int b, int nchunk, int chunk, int piece, int half, int Hp, int Wp) {
+  return img + ((((size_t)b * nchunk + chunk) * 2 + piece) * 2 + half) * Hp * Wp;
+}
+// the 8 channels channel(0) .. channel(7) of one position, split into the position's hi and lo vectors
+template <class F>
+__device__ __forceinline__ void split8(F channel, u32x4& qh, u32x4& ql) {
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    unsigned ph, pl;
+    split2(channel(2 * j), channel(2 * j + 1), ph, pl);
+    qh[j] = ph; ql[j] = pl;
+  }
 }
 
 }  // namespace ds_h3

@@ -9,19 +9,16 @@
 //   - anything else (H*W not a multiple of 4, or larger): a two-read fallback.
 // Statistics are two-pass in registers (mean, then centred second moment), fp32.
 #include "ds_common.h"
+#include "ds_h3_common.h"
+#include "ds_stream.h"
 
 namespace {
 
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-
-__device__ __forceinline__ float silu(float v) { return v / (1.0f + __expf(-v)); }
-
-// exact-ish exp: use expf (ocml, <= 1 ulp) rather than the fast intrinsic
-__device__ __forceinline__ float silu_precise(float v) { return v / (1.0f + expf(-v)); }
+using ds::silu;
+using ds::wave_sum;
+using ds_h3::image_plane;
+using ds_h3::split8;
+using ds_h3::u32x4;
 
 template <int KIND>
 __device__ __forceinline__ float apply_one(float v, float mean, float scale_or_denom, float w, float b) {
@@ -31,7 +28,7 @@ __device__ __forceinline__ float apply_one(float v, float mean, float scale_or_d
   } else {
     y = v / scale_or_denom * w + b;            // scale_or_denom = sqrt(mean(x^2)+eps), commonlayers.py:377-383
   }
-  return silu_precise(y);
+  return silu(y);
 }
 
 // ---- one wave per plane ---------------------------------------------------------------
@@ -232,7 +229,7 @@ __global__ __launch_bounds__(256) void k_pointwise_silu(float* out, const float*
       v = v / sqrtf(v * v + eps);
       v = v * wc + bc;
     }
-    op[i] = v / (1.0f + expf(-v));
+    op[i] = silu(v);
   }
 }
 
@@ -243,21 +240,8 @@ __global__ __launch_bounds__(256) void k_pointwise_silu(float* out, const float*
 // One workgroup of 8 waves per 8-channel group: wave k normalises channel k exactly as k_inorm_wave does (same loads, same
 // summation order, same activation: bit-identical values), parks its plane in LDS, then all threads gather the 8 channels of a
 // pixel, split and store two vectors.
-typedef _Float16 f16x2_t __attribute__((ext_vector_type(2)));
-typedef unsigned u32x4_t __attribute__((ext_vector_type(4)));
-
-__device__ __forceinline__ void split2_img(float a, float b, unsigned& hi, unsigned& lo) {      // ds_h3_common.h's split2
-  f16x2_t h = {(_Float16)a, (_Float16)b};
-  unsigned hp = __builtin_bit_cast(unsigned, h);
-  asm volatile("" : "+v"(hp));
-  const f16x2_t hq = __builtin_bit_cast(f16x2_t, hp);
-  f16x2_t l = {(_Float16)(a - (float)hq[0]), (_Float16)(b - (float)hq[1])};
-  hi = hp;
-  lo = __builtin_bit_cast(unsigned, l);
-}
-
 template <int KIND, int VPT>
-__global__ __launch_bounds__(512) void k_inorm_images(u32x4_t* __restrict__ img, const float* __restrict__ x,
+__global__ __launch_bounds__(512) void k_inorm_images(u32x4* __restrict__ img, const float* __restrict__ x,
                                                      const float* __restrict__ w, const float* __restrict__ b, int C, int nchunk,
                                                      int H, int W, int hw4, float inv_hw, float eps) {
   __shared__ __attribute__((aligned(16))) float act[8][1024];
@@ -309,8 +293,8 @@ __global__ __launch_bounds__(512) void k_inorm_images(u32x4_t* __restrict__ img,
     for (int i = 0; i < VPT; ++i) v[i] = make_float4(0, 0, 0, 0);
   }
   const int Hp = H + 2, Wp = W + 2, HW = 4 * hw4;
-  u32x4_t* hi_img = img + ((((size_t)bb * nchunk + chunk) * 2 + 0) * 2 + h) * Hp * Wp;
-  u32x4_t* lo_img = img + ((((size_t)bb * nchunk + chunk) * 2 + 1) * 2 + h) * Hp * Wp;
+  u32x4* hi_img = image_plane(img, bb, nchunk, chunk, 0, h, Hp, Wp);
+  u32x4* lo_img = image_plane(img, bb, nchunk, chunk, 1, h, Hp, Wp);
   // slabs of 1024 pixels (= 256 float4 = registers 4 s .. 4 s + 3 of every lane) through LDS: gather the 8 channels of a
   // pixel, split, store two vectors
   constexpr int NSLAB = (VPT + 3) / 4;
@@ -327,13 +311,8 @@ __global__ __launch_bounds__(512) void k_inorm_images(u32x4_t* __restrict__ img,
       const int i = 1024 * sl + j;
       if (i < HW) {
         const int y = i / W, xx = i - y * W;
-        u32x4_t qh, ql;
-#pragma unroll
-        for (int t = 0; t < 4; ++t) {
-          unsigned ph, pl;
-          split2_img(act[2 * t][j], act[2 * t + 1][j], ph, pl);
-          qh[t] = ph; ql[t] = pl;
-        }
+        u32x4 qh, ql;
+        split8([&](int k) { return act[k][j]; }, qh, ql);
         const size_t o = (size_t)(y + 1) * Wp + xx + 1;
         hi_img[o] = qh;
         lo_img[o] = ql;
@@ -341,7 +320,7 @@ __global__ __launch_bounds__(512) void k_inorm_images(u32x4_t* __restrict__ img,
     }
   }
   const int nb = 2 * Wp + 2 * H;                                   // the zero border (the convolution's padding)
-  const u32x4_t z = {0u, 0u, 0u, 0u};
+  const u32x4 z = {0u, 0u, 0u, 0u};
   for (int j = threadIdx.x; j < nb; j += 512) {
     size_t o;
     if (j < Wp) o = j;
@@ -395,7 +374,7 @@ extern "C" int ds_inorm_silu_images(void* images, const float* x, const float* w
   const float inv = 1.0f / (float)(H * W);
   hipStream_t s = ds::as_stream(stream);
   const dim3 g((unsigned)(B * nchunk * 2)), t(512);
-  u32x4_t* img = reinterpret_cast<u32x4_t*>(images);
+  u32x4* img = reinterpret_cast<u32x4*>(images);
 #define DS_LI(K) \
   do { \
     if (hw4 <= 64) hipLaunchKernelGGL((k_inorm_images<K, 1>), g, t, 0, s, img, x, w, b, C, nchunk, H, W, hw4, inv, eps); \

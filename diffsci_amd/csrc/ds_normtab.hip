@@ -19,6 +19,7 @@
 // (commonlayers.py:766-770: (x - mean)/sqrt(var + 1e-5) of a tensor of rms 1e-7 is 3e-5, not 1).  The value rides in the rows
 // the loader reads anyway: no extra load, no atomics.
 #include "ds_normtab_common.h"
+#include "ds_stream.h"
 
 namespace {
 
@@ -142,7 +143,7 @@ __global__ __launch_bounds__(G1T) void k_gnorm1_table(float* table, const float*
     reinterpret_cast<float4*>(table)[(size_t)b * Cpad + c] = o;
     U = fmaxf(U, fabsf(o.y) * dev + fabsf(o.z));
   }
-  for (int o = 32; o > 0; o >>= 1) U = fmaxf(U, __shfl_xor(U, o, 64));
+  U = ds::wave_max(U);
   if ((threadIdx.x & 63) == 0 && U > 0.f) atomicMax(&smax, __builtin_bit_cast(unsigned, U));    // LDS
   __syncthreads();
   const float inv = inv_scale_of(__builtin_bit_cast(float, smax));

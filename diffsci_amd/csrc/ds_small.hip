@@ -3,14 +3,12 @@
 // the whole batch during sampling -- schedulers.py:254), so they are written for clarity and
 // exactness, not for a roofline: fp32 FMA-free dot products reduced across a 64-lane wave.
 #include "ds_common.h"
+#include "ds_stream.h"
 
 namespace {
 
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
+using ds::wave_max;
+using ds::wave_sum;
 
 // one wave per output column n; the wave walks all rows m
 __global__ __launch_bounds__(256) void k_linear(float* y, const float* __restrict__ x, const float* __restrict__ w,
@@ -141,14 +139,14 @@ __global__ __launch_bounds__(64) void k_attn_generic(float* out, const float* __
     ps[k] = s;
     mx = fmaxf(mx, s);
   }
-  for (int o = 32; o > 0; o >>= 1) mx = fmaxf(mx, __shfl_xor(mx, o, 64));
+  mx = wave_max(mx);
   float sum = 0.f;
   for (int k = lane; k < L; k += 64) {
     const float p = expf(ps[k] - mx);
     ps[k] = p;
     sum += p;
   }
-  for (int o = 32; o > 0; o >>= 1) sum += __shfl_xor(sum, o, 64);
+  sum = wave_sum(sum);
   __syncthreads();
   const float inv = 1.0f / sum;
   for (int d = lane; d < E; d += 64) {

@@ -9,19 +9,14 @@
 // Everything is HBM-bound: one read and one write of the tensor (two reads for the gate), no matrix cores.  Arithmetic is
 // one rounding per operation (-ffp-contract=off), the patch linears are fmaf chains in k order.
 #include "ds_common.h"
+#include "ds_stream.h"
 
 namespace {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
+using ds::f32x4;
+using ds::silu;
+using ds::wave_commit_max_always;
 constexpr int NT = 256;
-
-__device__ __forceinline__ float silu(float v) { return v / (1.0f + expf(-v)); }
-
-__device__ __forceinline__ void wave_commit_max(unsigned* slot, float m) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o, 64));
-  if ((threadIdx.x & 63) == 0) atomicMax(slot, __builtin_bit_cast(unsigned, m));   // non-negative floats order like their bits
-}
 
 // ---- LayerNorm(E) + adaLN modulation ------------------------------------------------------------------------------------------
 // A workgroup owns 32 consecutive tokens of one sample: TX = 32 / VEC lanes along the tokens (VEC = 4: 16-byte loads, L % 4 == 0;
@@ -133,7 +128,7 @@ __global__ __launch_bounds__(NT) void k_token_ln(float* __restrict__ out, const 
       }
     }
   }
-  if (out_amax) wave_commit_max(out_amax + b, amax);
+  if (out_amax) wave_commit_max_always(out_amax + b, amax);
 }
 
 // ---- gated residual: out = x + gate[b, e] * y (a rounded product, then a rounded sum) -------------------------------------------
@@ -177,7 +172,7 @@ __global__ __launch_bounds__(NT) void k_silu_amax(float* out, const float* x, si
       out[base + i] = v;
     }
   }
-  if (out_amax) wave_commit_max(out_amax + blockIdx.y, m);
+  if (out_amax) wave_commit_max_always(out_amax + blockIdx.y, m);
 }
 
 // ---- patch embed: out[b, e, l] = bias[e] + sum_k W[e, k] * x[b, c, h p + p1, w p + p2], k = (c p + p1) p + p2, l = h Wp + w -----

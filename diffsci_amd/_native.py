@@ -14,6 +14,7 @@ ABI_VERSION = 4
 DS_IN_NETWORK, DS_IN_SCORE, DS_IN_DRIFT, DS_IN_FLOW = 0, 1, 2, 3
 DS_LOAD_PLAIN, DS_LOAD_MAXPOOL2, DS_LOAD_UPSAMPLE2, DS_LOAD_AVGPOOL2 = 0, 1, 2, 3
 DS_PAD_CIRCULAR = 16
+DS_PAD_ZERO_H, DS_PAD_ZERO_W, DS_PAD_ZERO_D = 64, 128, 0x10000   # with DS_PAD_CIRCULAR: this axis is zero-padded instead
 DS_RES1_UPSAMPLED = 32
 DS_PC_RAW, DS_PC_IMAGES = 1, 2
 DS_SI_BLEND, DS_SI_RENOISE = 1, 2

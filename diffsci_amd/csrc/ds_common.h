@@ -40,6 +40,20 @@ inline int ensure_dynamic_lds(int bytes, const char* what) {
   return DS_OK;
 }
 
+// The periodic axes of a convolution launch, as the kernels carry them: one wrap bit per axis, 0 = zero padding everywhere.
+enum { WRAP_H = 1, WRAP_W = 2, WRAP_D = 4 };
+
+// DS_PAD_CIRCULAR and the DS_PAD_ZERO_* bits of a load_mode / flags word -> wrap bits, or -1 for an undefined combination
+// (a zero bit without DS_PAD_CIRCULAR, no periodic axis left, DS_PAD_ZERO_D on a field).  DS_PAD_CIRCULAR alone: every axis.
+inline int wrap_axes(int word, bool volume) {
+  const int zero = word & (DS_PAD_ZERO_H | DS_PAD_ZERO_W | DS_PAD_ZERO_D);
+  if (!(word & DS_PAD_CIRCULAR)) return zero ? -1 : 0;
+  if ((zero & DS_PAD_ZERO_D) && !volume) return -1;
+  const int all = WRAP_H | WRAP_W | (volume ? WRAP_D : 0);
+  const int axes = all & ~((zero & DS_PAD_ZERO_H ? WRAP_H : 0) | (zero & DS_PAD_ZERO_W ? WRAP_W : 0) | (zero & DS_PAD_ZERO_D ? WRAP_D : 0));
+  return axes ? axes : -1;
+}
+
 }  // namespace ds
 
 #define DS_REQUIRE(cond, code, ...)  \

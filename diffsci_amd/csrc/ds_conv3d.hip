@@ -32,6 +32,7 @@ struct C3Args {
   int B, Cin, Cout, D, H, W;      // output volume
   int Di, Hi, Wi;                 // input volume (2x for MAXPOOL2, /2 for UPSAMPLE2)
   int tiles_y, tiles_x;
+  int circular;                   // ds::WRAP_D | ds::WRAP_H | ds::WRAP_W bits of the CIRC instances
 };
 
 __device__ __forceinline__ int wrap(int g, int n) {
@@ -73,8 +74,10 @@ __global__ __launch_bounds__(NT) void k_conv3d(const C3Args a) {
         if (CIRC) {
           // a ragged tile may reach more than one voxel past the volume: those positions only feed outputs that are
           // never stored; clamp after the single wrap
-          gz = wrap(gz, a.D); gy = wrap(gy, a.H); gx = wrap(gx, a.W);
-          gz = gz >= a.D ? a.D - 1 : gz; gy = gy >= a.H ? a.H - 1 : gy; gx = gx >= a.W ? a.W - 1 : gx;
+          // (a.circular: one wrap bit per axis; an axis without its bit keeps the zero padding)
+          if (a.circular & ds::WRAP_D) { gz = wrap(gz, a.D); gz = gz >= a.D ? a.D - 1 : gz; }
+          if (a.circular & ds::WRAP_H) { gy = wrap(gy, a.H); gy = gy >= a.H ? a.H - 1 : gy; }
+          if (a.circular & ds::WRAP_W) { gx = wrap(gx, a.W); gx = gx >= a.W ? a.W - 1 : gx; }
         }
         if (gz >= 0 && gz < a.D && gy >= 0 && gy < a.H && gx >= 0 && gx < a.W) {
           const float* p = in_b + (size_t)(c0 + c) * in_plane;
@@ -145,12 +148,12 @@ __global__ __launch_bounds__(NT) void k_conv3d(const C3Args a) {
 }
 
 template <int MODE>
-int launch3d(const C3Args& a, bool circ, hipStream_t s) {
+int launch3d(const C3Args& a, hipStream_t s) {
   const long long tiles = (long long)((a.D + TZ - 1) / TZ) * a.tiles_y * a.tiles_x;
   const int cots = (a.Cout + CO - 1) / CO;
   DS_REQUIRE(tiles < (1ll << 31) && cots < 65536 && a.B < 65536, DS_ERR_SHAPE, "ds_conv3d_direct: grid too large");
   dim3 g((unsigned)tiles, (unsigned)cots, (unsigned)a.B);
-  if (circ) hipLaunchKernelGGL((k_conv3d<MODE, true>), g, dim3(NT), 0, s, a);
+  if (a.circular) hipLaunchKernelGGL((k_conv3d<MODE, true>), g, dim3(NT), 0, s, a);
   else hipLaunchKernelGGL((k_conv3d<MODE, false>), g, dim3(NT), 0, s, a);
   DS_CHECK_LAUNCH("ds_conv3d_direct");
   return DS_OK;
@@ -164,8 +167,9 @@ extern "C" int ds_conv3d_direct(float* out, const float* in, const float* w, con
   DS_REQUIRE(out && in && w, DS_ERR_NULL, "ds_conv3d_direct: NULL pointer");
   DS_REQUIRE(B >= 0 && Cin > 0 && Cout > 0 && D > 0 && H > 0 && W > 0, DS_ERR_SHAPE,
              "ds_conv3d_direct: bad shape B=%d Cin=%d Cout=%d D=%d H=%d W=%d", B, Cin, Cout, D, H, W);
-  const bool circ = (load_mode & DS_PAD_CIRCULAR) != 0;
-  load_mode &= ~DS_PAD_CIRCULAR;
+  const int circular = ds::wrap_axes(load_mode, true);
+  DS_REQUIRE(circular >= 0, DS_ERR_UNSUPPORTED, "ds_conv3d_direct: load_mode %d (DS_PAD_ZERO_D / _H / _W go with DS_PAD_CIRCULAR and leave one axis periodic)", load_mode);
+  load_mode &= ~(DS_PAD_CIRCULAR | DS_PAD_ZERO_D | DS_PAD_ZERO_H | DS_PAD_ZERO_W);
   DS_REQUIRE(load_mode == DS_LOAD_PLAIN || load_mode == DS_LOAD_MAXPOOL2 || load_mode == DS_LOAD_UPSAMPLE2,
              DS_ERR_UNSUPPORTED, "ds_conv3d_direct: load_mode %d", load_mode);
   DS_REQUIRE(load_mode != DS_LOAD_UPSAMPLE2 || (D % 2 == 0 && H % 2 == 0 && W % 2 == 0), DS_ERR_SHAPE,
@@ -175,7 +179,7 @@ extern "C" int ds_conv3d_direct(float* out, const float* in, const float* w, con
   if (B == 0) return DS_OK;
   C3Args a;
   a.out = out; a.in = in; a.w = w; a.bias = bias; a.shift = shift; a.res1 = res1; a.res2 = res2;
-  a.shift_stride = shift_stride;
+  a.shift_stride = shift_stride; a.circular = circular;
   a.B = B; a.Cin = Cin; a.Cout = Cout; a.D = D; a.H = H; a.W = W;
   const int f2 = load_mode == DS_LOAD_MAXPOOL2 ? 2 : 1;
   a.Di = load_mode == DS_LOAD_UPSAMPLE2 ? D / 2 : D * f2;
@@ -183,9 +187,9 @@ extern "C" int ds_conv3d_direct(float* out, const float* in, const float* w, con
   a.Wi = load_mode == DS_LOAD_UPSAMPLE2 ? W / 2 : W * f2;
   a.tiles_y = (H + TY - 1) / TY; a.tiles_x = (W + TX - 1) / TX;
   hipStream_t s = ds::as_stream(stream);
-  if (load_mode == DS_LOAD_PLAIN) return launch3d<DS_LOAD_PLAIN>(a, circ, s);
-  if (load_mode == DS_LOAD_MAXPOOL2) return launch3d<DS_LOAD_MAXPOOL2>(a, circ, s);
-  return launch3d<DS_LOAD_UPSAMPLE2>(a, circ, s);
+  if (load_mode == DS_LOAD_PLAIN) return launch3d<DS_LOAD_PLAIN>(a, s);
+  if (load_mode == DS_LOAD_MAXPOOL2) return launch3d<DS_LOAD_MAXPOOL2>(a, s);
+  return launch3d<DS_LOAD_UPSAMPLE2>(a, s);
 }
 
 // ---------------------------------------------------------------------------------------------------------------

@@ -164,10 +164,9 @@ __global__ __launch_bounds__(64 * NW, TWO ? 2 : NW / 2) void k_conv3h(const Conv
       // wrap instead of zero padding: one halo pixel on either side, so a compare-and-add per edge
       // (no integer division: that cost 2-3 % of the whole kernel in the prologue); rows / columns
       // further outside only feed outputs of a ragged tile that are never stored -- clamp them
-      gy = gy < 0 ? gy + a.H : (gy >= a.H ? gy - a.H : gy);
-      gx = gx < 0 ? gx + a.W : (gx >= a.W ? gx - a.W : gx);
-      gy = gy >= a.H ? a.H - 1 : gy;
-      gx = gx >= a.W ? a.W - 1 : gx;
+      // (a.circular: one wrap bit per axis, wave-uniform; an axis without its bit keeps the zero padding: ok is false outside)
+      if (a.circular & ds::WRAP_H) { gy = gy < 0 ? gy + a.H : (gy >= a.H ? gy - a.H : gy); gy = gy >= a.H ? a.H - 1 : gy; }
+      if (a.circular & ds::WRAP_W) { gx = gx < 0 ? gx + a.W : (gx >= a.W ? gx - a.W : gx); gx = gx >= a.W ? a.W - 1 : gx; }
     }
     const bool ok = live && gy >= 0 && gy < a.H && gx >= 0 && gx < a.W;
     int off;
@@ -202,7 +201,7 @@ __global__ __launch_bounds__(64 * NW, TWO ? 2 : NW / 2) void k_conv3h(const Conv
         if (Gp < 8) { r = 4 * (Gp >> 2) + ((u >> 3) & 3); g = 2 * (Gp & 3) + ((u >> 2) & 1); }
         else { r = 8 + ((u >> 3) & 1); g = 4 * (Gp - 8) + 2 * ((u >> 4) & 1) + ((u >> 2) & 1); }
         int gy = y0 + r - 1 + a.oy;
-        if (CIRC) { gy = gy < 0 ? gy + a.H : (gy >= a.H ? gy - a.H : gy); gy = gy >= a.H ? a.H - 1 : gy; }
+        if (CIRC && (a.circular & ds::WRAP_H)) { gy = gy < 0 ? gy + a.H : (gy >= a.H ? gy - a.H : gy); gy = gy >= a.H ? a.H - 1 : gy; }
         const bool ok = gy >= 0 && gy < a.H;
         voff[i] = (8 * h + 2 * q) * HWin + (ok ? gy * a.Win + x0 + 4 * g : 0);
         vlds[i] = 16 * (h * HS + r * PW + 1 + 4 * g) + 4 * q;
@@ -214,9 +213,8 @@ __global__ __launch_bounds__(64 * NW, TWO ? 2 : NW / 2) void k_conv3h(const Conv
         const int r = e >> 1, col = (e & 1) ? PW - 1 : 0;
         int gy = y0 + r - 1 + a.oy, gx = x0 + col - 1;
         if (CIRC) {
-          gy = gy < 0 ? gy + a.H : (gy >= a.H ? gy - a.H : gy);
-          gx = gx < 0 ? gx + a.W : (gx >= a.W ? gx - a.W : gx);
-          gy = gy >= a.H ? a.H - 1 : gy;
+          if (a.circular & ds::WRAP_H) { gy = gy < 0 ? gy + a.H : (gy >= a.H ? gy - a.H : gy); gy = gy >= a.H ? a.H - 1 : gy; }
+          if (a.circular & ds::WRAP_W) gx = gx < 0 ? gx + a.W : (gx >= a.W ? gx - a.W : gx);
         }
         const bool ok = lane < 20 && gy >= 0 && gy < a.H && gx >= 0 && gx < a.W;
         voff[i] = 8 * h * HWin + (ok ? gy * a.Win + gx : 0);
@@ -835,15 +833,16 @@ static int conv2d_h3(float* out, const float* in, const void* w_packed, int wshi
   DS_REQUIRE(!(prenorm && in_amax), DS_ERR_UNSUPPORTED, "ds_conv2d_h3: in_amax is for raw inputs (with prenorm the table's fourth column carries the exponent)");
   DS_REQUIRE(B >= 0 && Cin > 0 && Cout > 0 && H > 0 && W > 0, DS_ERR_SHAPE,
              "ds_conv2d_h3: bad shape B=%d Cin=%d Cout=%d H=%d W=%d", B, Cin, Cout, H, W);
-  const int circular = (load_mode & DS_PAD_CIRCULAR) ? 1 : 0;
+  const int circular = ds::wrap_axes(load_mode, false);   // wrap bits, H and W
+  DS_REQUIRE(circular >= 0, DS_ERR_UNSUPPORTED, "ds_conv2d_h3: load_mode %d (DS_PAD_ZERO_H / _W go with DS_PAD_CIRCULAR and leave one axis periodic)", load_mode);
   const int res1_up = (load_mode & DS_RES1_UPSAMPLED) ? 1 : 0;
   // tap-origin offset, two signed 4-bit fields (DS_TAP_OFFSET): 0 for a plain 3x3 convolution
   const int oy = (int)((load_mode >> 8) & 15) - (((load_mode >> 8) & 8) ? 16 : 0);
   const int ox = (int)((load_mode >> 12) & 15) - (((load_mode >> 12) & 8) ? 16 : 0);
-  load_mode &= ~(DS_PAD_CIRCULAR | DS_RES1_UPSAMPLED | 0xff00);
+  load_mode &= ~(DS_PAD_CIRCULAR | DS_PAD_ZERO_H | DS_PAD_ZERO_W | DS_PAD_ZERO_D | DS_RES1_UPSAMPLED | 0xff00);
   // periodic padding with a tap offset (k x k kernels as shifted 3x3 blocks): the loader wraps once per edge, which covers a window
   // that reaches |offset| + 1 pixels outside on a plane at least that large (torch's own limit for F.pad(mode="circular"))
-  DS_REQUIRE(!circular || (H >= (oy < 0 ? -oy : oy) + 1 && W >= (ox < 0 ? -ox : ox) + 1), DS_ERR_SHAPE,
+  DS_REQUIRE((!(circular & ds::WRAP_H) || H >= (oy < 0 ? -oy : oy) + 1) && (!(circular & ds::WRAP_W) || W >= (ox < 0 ? -ox : ox) + 1), DS_ERR_SHAPE,
              "ds_conv2d_h3: periodic padding with tap offset (%d, %d) needs a field at least as large as the window's reach (%d x %d)", oy, ox, H, W);
   DS_REQUIRE(!res1_up || (res1 && H % 2 == 0 && W % 2 == 0), DS_ERR_SHAPE, "ds_conv2d_h3: RES1_UPSAMPLED needs res1 and even H, W");
   DS_REQUIRE(load_mode >= 0 && load_mode <= 2, DS_ERR_UNSUPPORTED, "ds_conv2d_h3: load_mode %d", load_mode);

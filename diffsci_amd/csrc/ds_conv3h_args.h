@@ -59,7 +59,7 @@ struct Conv3hArgs {
   int wshift;                // the packed weights carry 2^wshift
   int shift_stride;
   int res1_up;            // res1 is at half resolution (see ds_conv_epilogue.h)
-  int circular;           // periodic padding in both dimensions (CircularConv2d, commonlayers.py:918-971)
+  int circular;           // periodic padding (CircularConv2d, commonlayers.py:918-971): ds::WRAP_H | ds::WRAP_W bits, 0 = zero padding
   int oy, ox;             // tap-origin offset: the 3x3 window is centred at (y + oy, x + ox) -- sub-kernels of larger kernels
   int B, Cin, Cout, H, W, Hin, Win;
   int tiles_x, tiles_y, n_cot, n_chunks;

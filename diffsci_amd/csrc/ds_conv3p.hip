@@ -130,9 +130,10 @@ __device__ __forceinline__ unsigned const_u32(const void* p, size_t i) {
 // POOL: the store phase also writes MaxPool2d(2) of the stored values to a.pool_out [B, Cout, H/2, W/2] (the DownSampler's input, so
 // that its loader need not read four raw pixels per element once per channel tile).  A template parameter for NRES's reason: the
 // launches that do not pool keep their instruction stream.  Only the forms the last block of a level can be (static_assert).
-template <bool PRE, bool CIRC, int NRES, bool VEC = false, bool IMG = false, bool POOL = false>
+template <bool PRE, bool CIRC, int NRES, bool VEC = false, bool IMG = false, bool POOL = false, bool AXES = false>
 __global__ __launch_bounds__(512, 2) void k_conv3p(const Conv3hArgs a) {
   static_assert(!IMG || (!PRE && !CIRC && !VEC), "image input: plain zero-padded form");
+  static_assert(!AXES || CIRC, "per-axis wrap flags (a.circular): a form of the periodic instance; without AXES every axis wraps");
   static_assert(!POOL || ((PRE || IMG) && !CIRC && NRES >= 1), "pooled output: a residual block's second convolution, zero padding");
   constexpr int PW = Geo<false>::PW, NPOS = Geo<false>::NPOS;
   constexpr int HS = NPOS + HPAD16, PS = 2 * NPOS + HPAD16, XBV = XBUF_VEC16;
@@ -346,10 +347,13 @@ __global__ __launch_bounds__(512, 2) void k_conv3p(const Conv3hArgs a) {
       for (int i = 0; i < XI; ++i) {
         const bool halo = i == XI - 1 && pw >= 2;
         int gy = it.y0 + vr[i] - 1 + a.oy, gx = it.x0 + vx[i];
-        if (CIRC) {
+        if (CIRC && !AXES) {                                // every axis wraps
           gy = gy < 0 ? gy + a.H : (gy >= a.H ? gy - a.H : gy);
           gx = gx < 0 ? gx + a.W : (gx >= a.W ? gx - a.W : gx);
           gy = gy >= a.H ? a.H - 1 : gy;
+        } else if (CIRC) {                         // a.circular: one wrap bit per axis; an axis without its bit keeps the zero padding
+          if (a.circular & ds::WRAP_H) { gy = gy < 0 ? gy + a.H : (gy >= a.H ? gy - a.H : gy); gy = gy >= a.H ? a.H - 1 : gy; }
+          if (a.circular & ds::WRAP_W) gx = gx < 0 ? gx + a.W : (gx >= a.W ? gx - a.W : gx);
         }
         const bool ok = (!halo || halo_live) && gy >= 0 && gy < a.H && gx >= 0 && gx < a.W;
         xoff[i] = ok ? gy * a.W + gx : 0;
@@ -362,11 +366,14 @@ __global__ __launch_bounds__(512, 2) void k_conv3p(const Conv3hArgs a) {
 #pragma unroll
     for (int i = 0; i < XI; ++i) {
       int gy = it.y0 + xrow[i] - 1 + a.oy, gx = it.x0 + xcol[i] - 1 + a.ox;
-      if (CIRC) {
+      if (CIRC && !AXES) {
         gy = gy < 0 ? gy + a.H : (gy >= a.H ? gy - a.H : gy);
         gx = gx < 0 ? gx + a.W : (gx >= a.W ? gx - a.W : gx);
         gy = gy >= a.H ? a.H - 1 : gy;
         gx = gx >= a.W ? a.W - 1 : gx;
+      } else if (CIRC) {
+        if (a.circular & ds::WRAP_H) { gy = gy < 0 ? gy + a.H : (gy >= a.H ? gy - a.H : gy); gy = gy >= a.H ? a.H - 1 : gy; }
+        if (a.circular & ds::WRAP_W) { gx = gx < 0 ? gx + a.W : (gx >= a.W ? gx - a.W : gx); gx = gx >= a.W ? a.W - 1 : gx; }
       }
       const bool ok = live(i) && gy >= 0 && gy < a.H && gx >= 0 && gx < a.W;
       xoff[i] = ok ? gy * a.W + gx : 0;
@@ -971,11 +978,11 @@ __global__ __launch_bounds__(512, 2) void k_conv3p(const Conv3hArgs a) {
   }
 }
 
-template <bool PRE, bool CIRC, int NRES, bool VEC = false, bool IMG = false, bool POOL = false>
+template <bool PRE, bool CIRC, int NRES, bool VEC = false, bool IMG = false, bool POOL = false, bool AXES = false>
 int launch_conv3p_w(const Conv3hArgs& a, int wgs, hipStream_t s) {
-  const int rc = ds::ensure_dynamic_lds<&k_conv3p<PRE, CIRC, NRES, VEC, IMG, POOL>>(P_LDS, "hipFuncSetAttribute(conv3p)");
+  const int rc = ds::ensure_dynamic_lds<&k_conv3p<PRE, CIRC, NRES, VEC, IMG, POOL, AXES>>(P_LDS, "hipFuncSetAttribute(conv3p)");
   if (rc != DS_OK) return rc;
-  hipLaunchKernelGGL((k_conv3p<PRE, CIRC, NRES, VEC, IMG, POOL>), dim3((unsigned)wgs), dim3(512), P_LDS, s, a);
+  hipLaunchKernelGGL((k_conv3p<PRE, CIRC, NRES, VEC, IMG, POOL, AXES>), dim3((unsigned)wgs), dim3(512), P_LDS, s, a);
   DS_CHECK_LAUNCH("ds_conv2d_h3 (persistent)");
   return DS_OK;
 }
@@ -984,11 +991,11 @@ bool conv3p_vec() {
   static const bool on = [] { const char* e = getenv("DS_CONV_VEC"); return !(e && atoi(e) == 0); }();
   return on;
 }
-template <bool PRE, bool CIRC, int NRES, bool POOL = false>
+template <bool PRE, bool CIRC, int NRES, bool POOL = false, bool AXES = false>
 int launch_conv3p_r(const Conv3hArgs& a, int wgs, hipStream_t s) {
   // 16-byte patch loads: W is a multiple of 32 and Cin of 64 here (conv3p_try_launch); no column tap offset, an aligned input
-  if (conv3p_vec() && a.ox == 0 && (reinterpret_cast<uintptr_t>(a.in) & 15u) == 0) return launch_conv3p_w<PRE, CIRC, NRES, true, false, POOL>(a, wgs, s);
-  return launch_conv3p_w<PRE, CIRC, NRES, false, false, POOL>(a, wgs, s);
+  if (conv3p_vec() && a.ox == 0 && (reinterpret_cast<uintptr_t>(a.in) & 15u) == 0) return launch_conv3p_w<PRE, CIRC, NRES, true, false, POOL, AXES>(a, wgs, s);
+  return launch_conv3p_w<PRE, CIRC, NRES, false, false, POOL, AXES>(a, wgs, s);
 }
 // pooled output: a residual block's second convolution (at least one residual), zero padding, fused-loader or image input
 bool conv3p_pool_ok(const Conv3hArgs& a, bool img) {
@@ -1006,14 +1013,14 @@ void conv3p_fill_args(Conv3hArgs& a) {
   a.pc_skew_mask = skew;
   if (!a.res1 && a.res2) { a.res1 = a.res2; a.res2 = nullptr; }      // one residual: the order of the additions is the same
 }
-template <bool PRE, bool CIRC>
+template <bool PRE, bool CIRC, bool AXES = false>
 int launch_conv3p(Conv3hArgs a, int wgs, hipStream_t s) {
   conv3p_fill_args(a);
   if constexpr (PRE && !CIRC) {
     if (a.pool_out) return a.res2 ? launch_conv3p_r<PRE, CIRC, 2, true>(a, wgs, s) : launch_conv3p_r<PRE, CIRC, 1, true>(a, wgs, s);
   }
-  if (!a.res1) return launch_conv3p_r<PRE, CIRC, 0>(a, wgs, s);
-  return a.res2 ? launch_conv3p_r<PRE, CIRC, 2>(a, wgs, s) : launch_conv3p_r<PRE, CIRC, 1>(a, wgs, s);
+  if (!a.res1) return launch_conv3p_r<PRE, CIRC, 0, false, AXES>(a, wgs, s);
+  return a.res2 ? launch_conv3p_r<PRE, CIRC, 2, false, AXES>(a, wgs, s) : launch_conv3p_r<PRE, CIRC, 1, false, AXES>(a, wgs, s);
 }
 
 // DS_CONV_PC: 0 = never, 1 = the fused-loader launches with one channel tile, 2 (default since the consumers issue the weight DMA and the
@@ -1085,8 +1092,12 @@ int conv3p_try_launch(const Conv3hArgs& a0, hipStream_t s, bool* launched, bool 
   if (a.n_cot % 2 == 0 && a.prenorm && mode < 2) return DS_OK;     // the two-channel-tile kernel's launches
   if (!a.prenorm && mode < 3 && !raw) return DS_OK;   // raw-input launches: where the caller asks (ds_conv2d_h3_pc, DS_PC_RAW), or all of them (DS_CONV_PC=3)
   int rc;
-  if (a.prenorm) rc = a.circular ? launch_conv3p<true, true>(a, wgs, s) : launch_conv3p<true, false>(a, wgs, s);
-  else rc = a.circular ? launch_conv3p<false, true>(a, wgs, s) : launch_conv3p<false, false>(a, wgs, s);
+  // zero padding, every axis periodic (CIRC), or the axes flagged in a.circular (CIRC with AXES).  The plan is made once per item here,
+  // not once per workgroup, and the two flag tests cost the all-periodic launch 0.7 % at [64, 64, 128, 128]: it keeps its own instance
+  const bool all = a.circular == (ds::WRAP_H | ds::WRAP_W);
+#define DS_LP(P) (all ? launch_conv3p<P, true>(a, wgs, s) : (a.circular ? launch_conv3p<P, true, true>(a, wgs, s) : launch_conv3p<P, false>(a, wgs, s)))
+  rc = a.prenorm ? DS_LP(true) : DS_LP(false);
+#undef DS_LP
   if (rc == DS_OK) { *launched = true; if (pooled) *pooled = pool; }
   return rc;
 }

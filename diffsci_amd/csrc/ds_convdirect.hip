@@ -49,7 +49,7 @@ __global__ __launch_bounds__(NT) void k_conv_direct(float* out, const float* __r
     {
       const int col = tid & 63, r0 = tid >> 6;
       int gx0 = x0 + col - 1, gx1 = x0 + 64 + col - 1;
-      if (circular) {
+      if (circular & ds::WRAP_W) {                     // circular: one wrap bit per axis, 0 = zero padding
         gx0 = (gx0 < 0 ? gx0 + W : gx0) % W;
         gx1 = gx1 % W;
       }
@@ -60,7 +60,7 @@ __global__ __launch_bounds__(NT) void k_conv_direct(float* out, const float* __r
       for (int k = 0; k < NR; ++k) {
         const int r = r0 + 4 * k;
         int gy = y0 + r - 1;
-        if (circular) gy = (gy < 0 ? gy + H : gy) % H;
+        if (circular & ds::WRAP_H) gy = (gy < 0 ? gy + H : gy) % H;
         const bool oky = r < PH && gy >= 0 && gy < H;
         const float* src = in_b + (size_t)c0 * HW + (size_t)(oky ? gy : 0) * W;
 #pragma unroll
@@ -159,7 +159,7 @@ __global__ __launch_bounds__(NT, 4) void k_conv_direct_v(float* out, const float
     const int ch = idx / (PH * 16), rem = idx - ch * (PH * 16);
     const int r = rem >> 4, g = rem & 15;
     int gy = y0 + r - 1;
-    if (circular) gy = (gy < 0 ? gy + H : gy) % H;
+    if (circular & ds::WRAP_H) gy = (gy < 0 ? gy + H : gy) % H;
     const bool ok = gy >= 0 && gy < H;
     goff[k] = ch * (int)HW + (ok ? gy : 0) * W + x0 + 4 * g;
     loff[k] = ch * PATCH + r * PSTR + 1 + 4 * g;
@@ -175,7 +175,8 @@ __global__ __launch_bounds__(NT, 4) void k_conv_direct_v(float* out, const float
     const int ch = ii / (PH * 2), rem = ii - ch * (PH * 2);
     const int r = rem >> 1, side = rem & 1;
     int gy = y0 + r - 1, gx = side ? x0 + TW : x0 - 1;
-    if (circular) { gy = (gy < 0 ? gy + H : gy) % H; gx = (gx < 0 ? gx + W : gx) % W; }
+    if (circular & ds::WRAP_H) gy = (gy < 0 ? gy + H : gy) % H;
+    if (circular & ds::WRAP_W) gx = (gx < 0 ? gx + W : gx) % W;
     const bool ok = live && gy >= 0 && gy < H && gx >= 0 && gx < W;
     hgoff[k] = ch * (int)HW + (ok ? gy * W + gx : 0);
     hloff[k] = live ? ch * PATCH + r * PSTR + (side ? TW + 1 : 0) : -1;
@@ -254,6 +255,12 @@ extern "C" int ds_conv2d_direct(float* out, const float* in, const float* w, con
   DS_REQUIRE(B >= 0 && Cin > 0 && H > 0 && W > 0, DS_ERR_SHAPE, "ds_conv2d_direct: bad shape");
   DS_REQUIRE(Cout >= 1 && Cout <= 4, DS_ERR_UNSUPPORTED, "ds_conv2d_direct: Cout=%d (1..4 supported)", Cout);
   DS_REQUIRE((reinterpret_cast<uintptr_t>(out) & 15u) == 0, DS_ERR_SHAPE, "ds_conv2d_direct: out must be 16-byte aligned");
+  // 0, or 1 with DS_PAD_ZERO_H / DS_PAD_ZERO_W: the load_mode bits beside the historical "1 = every axis" -> wrap bits
+  if (circular) {
+    const int word = circular;
+    circular = (word & ~(DS_PAD_ZERO_H | DS_PAD_ZERO_W)) == 1 ? ds::wrap_axes(DS_PAD_CIRCULAR | (word & ~1), false) : -1;
+    DS_REQUIRE(circular > 0, DS_ERR_UNSUPPORTED, "ds_conv2d_direct: circular %d (0, 1, or 1 with DS_PAD_ZERO_H or DS_PAD_ZERO_W)", word);
+  }
   if (B == 0) return DS_OK;
   const int tiles_x = (W + TW - 1) / TW, tiles_y = (H + TH - 1) / TH;
   const long long blocks = (long long)B * tiles_x * tiles_y;

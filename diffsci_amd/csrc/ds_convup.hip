@@ -72,6 +72,7 @@ struct UpArgs {
   int wshift;
   int shift_stride;
   int res1_up;
+  int circular;           // ds::WRAP_H | ds::WRAP_W bits of the CIRC instances
   int B, Cin, Cout, Hl, Wl;
   int tiles_x, tiles_y, n_cot, n_chunks;
   unsigned tiles_x_magic;
@@ -247,8 +248,8 @@ __global__ __launch_bounds__(NT, 2) void k_convup(const UpArgs a) {
     const int col = pos - r * PW;
     int gy = y0 + r - 1 + pa, gx = x0 + col - 1;
     if (CIRC) {                                       // tiles divide the image: at most one pixel outside
-      gy = gy < 0 ? gy + a.Hl : (gy >= a.Hl ? gy - a.Hl : gy);
-      gx = gx < 0 ? gx + a.Wl : (gx >= a.Wl ? gx - a.Wl : gx);
+      if (a.circular & ds::WRAP_H) gy = gy < 0 ? gy + a.Hl : (gy >= a.Hl ? gy - a.Hl : gy);   // one wrap bit per axis; without it, zero padding
+      if (a.circular & ds::WRAP_W) gx = gx < 0 ? gx + a.Wl : (gx >= a.Wl ? gx - a.Wl : gx);
     }
     const bool ok = live && gy >= 0 && gy < a.Hl && gx >= 0 && gx < a.Wl;
     xoff[i] = ok ? gy * a.Wl + gx : 0;
@@ -645,7 +646,8 @@ int ds_conv2d_h3_up(float* out, const float* in, const void* w_packed, int wshif
   DS_REQUIRE(!(prenorm && in_amax), DS_ERR_UNSUPPORTED, "ds_conv2d_h3_up: in_amax is for raw inputs (with prenorm the table's fourth column carries the exponent)");
   DS_REQUIRE(B >= 0 && Cin > 0 && Cout > 0 && Hl > 0 && Wl > 0, DS_ERR_SHAPE,
              "ds_conv2d_h3_up: bad shape B=%d Cin=%d Cout=%d Hl=%d Wl=%d", B, Cin, Cout, Hl, Wl);
-  DS_REQUIRE((flags & ~(DS_PAD_CIRCULAR | DS_RES1_UPSAMPLED)) == 0, DS_ERR_UNSUPPORTED, "ds_conv2d_h3_up: flags %d", flags);
+  DS_REQUIRE((flags & ~(DS_PAD_CIRCULAR | DS_PAD_ZERO_H | DS_PAD_ZERO_W | DS_RES1_UPSAMPLED)) == 0 && ds::wrap_axes(flags, false) >= 0, DS_ERR_UNSUPPORTED,
+             "ds_conv2d_h3_up: flags %d", flags);
   const int geo = up_geometry(Hl, Wl);
   DS_REQUIRE(geo != 0, DS_ERR_UNSUPPORTED,
              "ds_conv2d_h3_up: %d x %d input is not a whole number of 8x32 or 16x16 tiles (use ds_conv2d_h3 with DS_LOAD_UPSAMPLE2)",
@@ -664,6 +666,7 @@ int ds_conv2d_h3_up(float* out, const float* in, const void* w_packed, int wshif
   a.out = out; a.in = in; a.wp = reinterpret_cast<const u32x4*>(w_packed); a.bias = bias; a.shift = shift;
   a.res1 = res1; a.res2 = res2; a.prenorm = prenorm; a.tile_stats = tile_stats;
   a.wshift = wshift; a.in_amax = in_amax; a.out_amax = out_amax; a.shift_stride = shift_stride; a.res1_up = res1_up;
+  a.circular = ds::wrap_axes(flags, false);
   a.B = B; a.Cin = Cin; a.Cout = Cout; a.Hl = Hl; a.Wl = Wl;
   const bool w16 = geo == 2;
   const int TW = w16 ? 16 : 32, TH = w16 ? 16 : 8;
@@ -672,7 +675,7 @@ int ds_conv2d_h3_up(float* out, const float* in, const void* w_packed, int wshif
   a.n_chunks = (Cin + KC - 1) / KC;
   a.tiles_x_magic = a.tiles_x == 1 ? 0u : (unsigned)((1ull << 32) / (unsigned)a.tiles_x) + 1u;
   hipStream_t s = ds::as_stream(stream);
-  const bool circ = flags & DS_PAD_CIRCULAR;
+  const bool circ = a.circular != 0;
 #define DS_LU(W) (prenorm ? (circ ? launch_up<W, true, true>(a, s) : launch_up<W, true, false>(a, s)) \
                           : (circ ? launch_up<W, false, true>(a, s) : launch_up<W, false, false>(a, s)))
   return w16 ? DS_LU(true) : DS_LU(false);
@@ -697,7 +700,7 @@ int ds_conv2d_h3_up_img(float* out, const void* images, const void* w_packed, in
   UpArgs a;
   a.out = out; a.in = reinterpret_cast<const float*>(images); a.wp = reinterpret_cast<const u32x4*>(w_packed); a.bias = bias;
   a.shift = shift; a.res1 = res1; a.res2 = res2; a.prenorm = nullptr; a.tile_stats = tile_stats;
-  a.wshift = wshift; a.in_amax = nullptr; a.out_amax = out_amax; a.shift_stride = shift_stride; a.res1_up = 0;
+  a.wshift = wshift; a.in_amax = nullptr; a.out_amax = out_amax; a.shift_stride = shift_stride; a.res1_up = 0; a.circular = 0;
   a.B = B; a.Cin = Cin; a.Cout = Cout; a.Hl = Hl; a.Wl = Wl;
   const bool w16 = geo == 2;
   const int TW = w16 ? 16 : 32, TH = w16 ? 16 : 8;

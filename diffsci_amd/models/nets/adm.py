@@ -38,6 +38,7 @@ from ... import ops
 from ..._native import DS_LOAD_AVGPOOL2, DS_LOAD_PLAIN, DS_LOAD_UPSAMPLE2
 from . import precision
 from . import runtime
+from .commonlayers import PeriodicAxes
 from .punetg import _AffineHolder, _Attn, _CircConv, _Fourier, make_conv
 from .runtime import AmaxArena, Workspace, _amax_kw, require_eval, shift_rows, weights_signature
 
@@ -174,7 +175,7 @@ class _Block(torch.nn.Module):
             self.attn = _Attn(cout)
 
 
-class ADMBaseBlock(torch.nn.Module):
+class ADMBaseBlock(PeriodicAxes, torch.nn.Module):
     """One ADM residual block as a module of its own -- the reference's ADMBaseBlock / ADMEncoderBlock / ADMDecoderBlock
     (adm.py:218-540), which its tests drive directly, on 2-D fields AND 3-D volumes (tests/test_adm.py:7-70):
 
@@ -228,7 +229,7 @@ class ADMBaseBlock(torch.nn.Module):
         cin = channels_in + channels_skip if (channels_skip and skip_integration_type == "concat") else channels_in
         self.channels_in_modified = cin
         circ = conv_type == "circular"
-        self.circular = circ
+        self.circular_axes = (circ,) * dimension           # which axes wrap (extra.convert_conv_to_circular sets a subset)
         self.norm1 = torch.nn.GroupNorm(1, cin, affine=affine_norm) if first_norm == "GroupLN" else _AffineHolder(cin, affine_norm)
         self.norm2 = (torch.nn.GroupNorm(1, channels_out, affine=affine_norm) if second_norm == "GroupLN"
                       else _AffineHolder(channels_out, affine_norm))
@@ -270,10 +271,10 @@ class ADMBaseBlock(torch.nn.Module):
         """3x3(x3) 'same' convolution of the block (with the nearest x2 upsampling in its loader when up)."""
         mode = DS_LOAD_UPSAMPLE2 if up else DS_LOAD_PLAIN
         if self.dimension == 2:
-            return ops.conv(x, pk[id(m)], bias=m.bias, circular=self.circular, load_mode=mode, res1=res1)
+            return ops.conv(x, pk[id(m)], bias=m.bias, circular=self.circular_arg, load_mode=mode, res1=res1)
         if id(m) in pk:
-            return ops.conv3d_mfma(x, pk[id(m)], bias=m.bias, circular=self.circular, load_mode=mode, res1=res1)
-        return ops.conv3d(x, m.weight, bias=m.bias, circular=self.circular, load_mode=mode, res1=res1)
+            return ops.conv3d_mfma(x, pk[id(m)], bias=m.bias, circular=self.circular_arg, load_mode=mode, res1=res1)
+        return ops.conv3d(x, m.weight, bias=m.bias, circular=self.circular_arg, load_mode=mode, res1=res1)
 
     @ops.device_guard
     def forward(self, x, te, skip=None):
@@ -610,7 +611,7 @@ class _Middle(torch.nn.Module):
         self.middle_blocks = torch.nn.ModuleList(blocks)
 
 
-class ADM(torch.nn.Module):
+class ADM(PeriodicAxes, torch.nn.Module):
     def __init__(self, config: ADMConfig, conditional_embedding: torch.nn.Module | None = None):
         super().__init__()
         why = config.unsupported_reason()
@@ -622,6 +623,9 @@ class ADM(torch.nn.Module):
         mult = config.extended_channel_expansion
         self.time_embedding = ADMTimeEmbedding(config.time_embed_dim, ce, config.time_projection_scale)
         circ = config.convolution_type == "circular"           # the blocks' convolutions; input/output layers stay zero-padded
+        # the axes a CircularConv2d of this net wraps ((H, W) bools): every launch of the walk takes them from here
+        # (extra.convert_conv_to_circular sets a subset, and makes the input / output layers periodic too)
+        self.circular_axes = (circ, circ)
         # ADMConfig.affine_norm never reaches the blocks in the reference (ADMEncoder / ADMMiddleBlock / ADMDecoder do
         # not forward it, adm.py:455-520,540-834): the norms are always affine, and checkpoints carry their weights
         nk = dict(norms=(config.first_resblock_norm, config.second_resblock_norm))
@@ -753,8 +757,17 @@ class ADM(torch.nn.Module):
         return pk
 
     # ------------------------------------------------------------------ the network
+    def drop_caches(self):
+        """commonlayers.PeriodicAxes.drop_caches, with this network's workspace and norm window cache."""
+        super().drop_caches()
+        self._ws, self._am, self._window_cache = Workspace(), None, {}
+
+    def _axes_of(self, m):
+        """circular= of a launch of convolution m: the net's axes where the layer is a CircularConv2d, zero padding elsewhere."""
+        return self.circular_arg if isinstance(m, _CircConv) else False
+
     def _conv(self, m, x, pk, in_amax=None, out_amax=None, **kw):
-        return ops.conv(x, pk[id(m)], bias=m.bias, circular=isinstance(m, _CircConv),
+        return ops.conv(x, pk[id(m)], bias=m.bias, circular=self._axes_of(m),
                         **_amax_kw(pk[id(m)], in_amax=in_amax, out_amax=out_amax), **kw)
 
     def _raw_amax(self, x, xa):
@@ -1004,7 +1017,7 @@ class ADM(torch.nn.Module):
         ha = slot()
         if am is not None and self.exact_input_layer:                               # see PUNetG.forward_with_shifts
             hs = None
-            h = ops.conv(x, pk[(id(self.input_layer), "exact")], bias=self.input_layer.bias,
+            h = ops.conv(x, pk[(id(self.input_layer), "exact")], bias=self.input_layer.bias, circular=self._axes_of(self.input_layer),
                          out=ws.take((B, cfg.model_channels, H, W), dev))
             ops.absmax_rows(h, out=ha)
         else:
@@ -1023,7 +1036,7 @@ class ADM(torch.nn.Module):
             give(s)
         m = self.output_layer
         if m.out_channels <= 4:                                                     # see PUNetG._out_conv
-            y = ops.conv_direct(a[0], m.weight, m.bias, out=out)
+            y = ops.conv_direct(a[0], m.weight, m.bias, circular=self._axes_of(m), out=out)
         else:
             y = self._conv(m, a[0], pk, out=out, in_amax=a[2])
         give(a)

@@ -24,7 +24,7 @@ import torch
 
 from ... import ops
 from ..._native import DS_LOAD_MAXPOOL2, DS_LOAD_UPSAMPLE2
-from . import precision, runtime
+from . import commonlayers, precision, runtime
 from .punetg_config import PUNetGConfig, scale_factor
 from .runtime import AmaxArena, Workspace, _amax_kw, require_eval, shift_rows, weights_signature
 
@@ -129,27 +129,14 @@ class _TimeBlock(torch.nn.Module):
             lin(4 * embed, out))
 
 
-class _CircConv(torch.nn.Module):
-    """CircularConv2d / CircularConv3d parameters (commonlayers.py:918-1040): the weights live one level down, in .conv."""
-
-    def __init__(self, cin, cout, k, bias=True, dim=2):
-        super().__init__()
-        self.conv = (torch.nn.Conv3d if dim == 3 else torch.nn.Conv2d)(cin, cout, k, bias=bias)
-        self.in_channels, self.out_channels = cin, cout
-
-    @property
-    def weight(self):
-        return self.conv.weight
-
-    @property
-    def bias(self):
-        return self.conv.bias
+# CircularConv2d / CircularConv3d (commonlayers.py:918-1040): the weights live one level down, in .conv
+_CircConv = commonlayers._CircularConv
 
 
 def make_conv(cin, cout, k, kind="default", bias=True, dim=2):
     """choose_conv_cls (punetg.py:217-236): kind = convolution_type ("default" | "circular" | "mp"), dim 2 or 3."""
     if kind is True or kind == "circular":
-        return _CircConv(cin, cout, k, bias, dim)
+        return (commonlayers.CircularConv3d if dim == 3 else commonlayers.CircularConv2d)(cin, cout, k, bias=bias)
     if kind == "mp":
         return _MPConv(cin, cout, k, bias, dim)
     return (torch.nn.Conv3d if dim == 3 else torch.nn.Conv2d)(cin, cout, k, padding="same", bias=bias)
@@ -277,7 +264,7 @@ class _FieldShifts:
             self.te_owned = False
 
 
-class PUNetG(torch.nn.Module):
+class PUNetG(commonlayers.PeriodicAxes, torch.nn.Module):
     def __init__(self,
                  config: PUNetGConfig,
                  conditional_embedding: torch.nn.Module | None = None,
@@ -301,7 +288,11 @@ class PUNetG(torch.nn.Module):
         self.conditional_embedding = conditional_embedding
         self.cond_drop = (_ConditionDrop(config.cond_drop, mc, config.cond_drop_learnable)
                           if config.cond_drop is not None and config.cond_drop > 0 else None)     # punetg.py:102-106
-        self.circular = config.convolution_type == "circular"
+        # periodic padding: circular_axes, one bool per spatial axis in tensor-axis order, is the one source (commonlayers.
+        # PeriodicAxes): `circular` = some axis wraps (the routes: no norm_images, no pool_route, no exact input layer),
+        # `circular_arg` = what every launch of the walk passes as circular=.  convolution_type "circular" is every axis;
+        # extra.convert_conv_to_circular sets a subset.
+        self.circular_axes = (config.convolution_type == "circular",) * config.dimension
         self.mp = config.convolution_type == "mp"
         self.cosine_attn = config.attn_type == "cosine"
         self.inhouse_attn = self.mp or self.cosine_attn        # attention.py:29-52
@@ -349,6 +340,14 @@ class PUNetG(torch.nn.Module):
         self._window_cache = {}
         # set by precision.escalate_input when the input's channels differ by more than 2^14 in magnitude within a sample
         self.exact_input_layer = False
+
+    def drop_caches(self):
+        """commonlayers.PeriodicAxes.drop_caches, with this network's own: the time blocks' packings, the workspace, the norm
+        window cache."""
+        super().drop_caches()
+        self.__dict__.pop("_tb_packed", None)
+        self.__dict__.pop("_tb_packed_sig", None)
+        self._ws, self._am, self._window_cache = Workspace(), None, {}
 
     # ------------------------------------------------------------------ builders (punetg.py:122-334: same names and arguments)
     def choose_conv_cls(self):
@@ -784,7 +783,7 @@ class PUNetG(torch.nn.Module):
 
     # ------------------------------------------------------------------ the network
     def _conv(self, m, x, pk, in_amax=None, out_amax=None, **kw):
-        return ops.conv(x, pk[id(m)], bias=m.bias, circular=self.circular, **_amax_kw(pk[id(m)], in_amax=in_amax, out_amax=out_amax), **kw)
+        return ops.conv(x, pk[id(m)], bias=m.bias, circular=self.circular_arg, **_amax_kw(pk[id(m)], in_amax=in_amax, out_amax=out_amax), **kw)
 
     def _out_is_direct(self, m):
         return m.out_channels <= 4 and getattr(self, "direct_out", True) and self.config.in_out_kernel_size == 3
@@ -1126,7 +1125,7 @@ class _Fields:
             # the input's channels are too far apart in magnitude for one exponent per sample (precision.escalate_input):
             # exact-fp32 kernel, no tile statistics (the first block normalises standalone)
             # (circular= : a periodic network with exact_input_layer set by hand must raise -- the exact-fp32 kernel zero-pads)
-            return ops.conv(x, self.pk[(id(m), "exact")], bias=m.bias, circular=net.circular, out=self.ws.take(shape, self.dev)), None, None
+            return ops.conv(x, self.pk[(id(m), "exact")], bias=m.bias, circular=net.circular_arg, out=self.ws.take(shape, self.dev)), None, None
         hs = self.stats(to, *shape[1:])
         wmax = self.pk.get((id(m), "wmax"))
         return net._conv(m, x, self.pk, tile_stats=hs, out=self.ws.take(shape, self.dev),
@@ -1183,7 +1182,7 @@ class _Fields:
 
     def out(self, a, out):
         net = self.net
-        return net._out_conv(net.convout, a[0], self.pk, out, net.circular, in_amax=None if self.direct_out else self.amax_of(a))
+        return net._out_conv(net.convout, a[0], self.pk, out, net.circular_arg, in_amax=None if self.direct_out else self.amax_of(a))
 
 
 class _Volumes:
@@ -1234,9 +1233,9 @@ class _Volumes:
                                       f"(conv_precision={net.conv_precision!r})")
         if packs is not None and ((m.out_channels > 4 and m.in_channels > 4) or k != 3):
             st = self.stats_buf(shape) if (self.fold and want_stats) else None
-            return ops.conv3d_mfma(h, packs, bias=m.bias, circular=net.circular, load_mode=load_mode, out=dst, ws=self.ws,
+            return ops.conv3d_mfma(h, packs, bias=m.bias, circular=net.circular_arg, load_mode=load_mode, out=dst, ws=self.ws,
                                    out_stats=st, in_amax=ops.NORMALISED if normalised else None, **kw), st, None
-        return ops.conv3d(h, pk.get((id(m), "eff"), m.weight), bias=m.bias, circular=net.circular, load_mode=load_mode,
+        return ops.conv3d(h, pk.get((id(m), "eff"), m.weight), bias=m.bias, circular=net.circular_arg, load_mode=load_mode,
                           out=dst, **kw), None, None
 
     def conv_in(self, x, to):
@@ -1257,7 +1256,7 @@ class _Volumes:
             tab = ops.inorm_table(hs, w1, b1, k1, h[0, 0].numel(), eps=1e-5, out=ws.take((B, ops.table_channels(C), 4), dev))
             os_ = self.stats_buf(h.shape) if want_stats else None
             y = ops.resblock3d_fused(h, tab, p1, blk.conv1.bias, self.sh(), p2, blk.conv2.bias, w2, b2, k2, res2=res2,
-                                     out=ws.take(h.shape, dev), out_stats=os_, ws=ws, circular=net.circular)
+                                     out=ws.take(h.shape, dev), out_stats=os_, ws=ws, circular=net.circular_arg)
             ws.give(tab)
             return y, os_, None
         act = ops.inorm_silu(h, w1, b1, kind=k1, eps=1e-5, out=ws.take(h.shape, dev))
@@ -1323,6 +1322,10 @@ class PUNetGCond(PUNetG):
         self.channel_conditional_items = channel_conditional_items
         self._ycat = None
         self._ycat_static = {}       # (shape, device) -> buffer holding the concatenated channel fields
+
+    def drop_caches(self):
+        super().drop_caches()
+        self._ycat, self._ycat_static = None, {}
 
     def export_description(self) -> dict[str, Any]:
         args = super().export_description()

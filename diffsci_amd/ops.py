@@ -561,9 +561,33 @@ def inorm_silu(x, w, b, kind, eps=1e-5, out=None):
     return out
 
 
+def circular_axes(circular, ndim):
+    """circular= of the convolutions as one bool per spatial axis, in tensor-axis order ((H, W) or (D, H, W)): False, True
+    (every axis), or a sequence of ndim bools (circular_dims of CircularConv2d / CircularConv3d, commonlayers.py:918-1034)."""
+    if not hasattr(circular, "__iter__"):
+        return (bool(circular),) * ndim
+    axes = tuple(bool(a) for a in circular)
+    if len(axes) != ndim:
+        raise ValueError(f"circular: one flag per spatial axis ({ndim}: {'(D, H, W)' if ndim == 3 else '(H, W)'}); got {len(axes)}")
+    return axes
+
+
+def pad_word(circular, ndim):
+    """The padding bits of a load_mode / flags word (include/diffsci_hip.h) for circular= (see circular_axes): 0 when no axis is
+    periodic, DS_PAD_CIRCULAR when all are, and DS_PAD_CIRCULAR with a DS_PAD_ZERO_* bit for every axis that stays zero-padded.
+    Pure: no library call."""
+    axes = circular_axes(circular, ndim)
+    if not any(axes):
+        return 0
+    zero = (N.DS_PAD_ZERO_D, N.DS_PAD_ZERO_H, N.DS_PAD_ZERO_W)[3 - ndim:]
+    return N.DS_PAD_CIRCULAR | sum(z for a, z in zip(axes, zero) if not a)
+
+
 def conv3d(x, w, bias=None, shift=None, res1=None, res2=None, load_mode=N.DS_LOAD_PLAIN, circular=False, out=None):
     """3x3x3 'same' convolution of a volume [B, Cin, Di, Hi, Wi] with raw torch weights [Cout, Cin, 3, 3, 3], exact
-    fp32; MaxPool3d(2) / nearest x2 upsampling fused in the loader; shift [1 or B, Cout]."""
+    fp32; MaxPool3d(2) / nearest x2 upsampling fused in the loader; shift [1 or B, Cout].  circular: False, True or
+    (D, H, W) flags (circular_axes)."""
+    pad = pad_word(circular, 3)
     require_device(x, "x")
     B, Cin, Di, Hi, Wi = x.shape
     Cout = w.shape[0]
@@ -576,7 +600,7 @@ def conv3d(x, w, bias=None, shift=None, res1=None, res2=None, load_mode=N.DS_LOA
     _entries(bias, Cout, "bias must have Cout entries")
     N.check(N.lib().ds_conv3d_direct(_p(out), _p(x.contiguous()), _p(w.contiguous()), _p(bias), _p(shift), stride, _p(res1),
                                      _p(res2), B, Cin, Cout, D, H, W,
-                                     load_mode | (N.DS_PAD_CIRCULAR if circular else 0), _stream()), "ds_conv3d_direct")
+                                     load_mode | pad, _stream()), "ds_conv3d_direct")
     return out
 
 
@@ -613,7 +637,7 @@ def _depth_taps(s_in, s_out, packs, bias, rows, load_mode, circular, prenorm=Non
     tap initialises the accumulator (all slices of s_out but the outermost k/2 on each end), the others add to it; prenorm:
     per-SLICE table [B*(D+2), ceil16(Cin), 4] (ds_slice_tables) for the fused norm + SiLU loader; tile_stats: filled by the last
     launch.  in_amax: per-SLICE max |s_in| [B*(D+2 pad)] (every slice is a 2-D sample with its own exponent), NORMALISED, or
-    None = computed here."""
+    None = computed here.  circular: the PLANE's padding, False, True or (H, W) flags; the depth is the pad slices' business."""
     ns = s_in.shape[0]
     P = len(packs) // 2
     acc = s_out[P:ns - P]
@@ -651,9 +675,11 @@ def resblock3d_fused(h, tab1, packs1, bias1, shift, packs2, bias2, w2, b2, kind2
         S3 = conv2(SiLU(norm2(S2))) three launches with the fused loader reading S2 in place
         out = S3 + h [+ res2]       by the slice -> volume copy, which also leaves out's statistics (out_stats)
     against norm, copy, 3 launches, copy, norm, copy, 3 launches, copy.  Plain loads, fp16x3 packings.  circular: periodic
-    padding on all three axes (commonlayers.py:918-971) -- in the plane by the convolution's loader, along the depth by pad
+    padding on all three axes, or (D, H, W) flags (commonlayers.py:918-1034) -- in the plane by the convolution's loader, along the depth by pad
     slices that hold wrapped copies: S1's from the volume -> slice copy, S2's from one small copy after conv1 (the pad rows of T
     are then the sample's row, not zeros)."""
+    wrap_d, *plane = circular_axes(circular, 3)
+    plane = tuple(plane)
     require_device(h, "h")
     B, C, D, H, W = h.shape
     if packs1[0].Cout != C or packs2[0].Cout != C:
@@ -665,22 +691,22 @@ def resblock3d_fused(h, tab1, packs1, bias1, shift, packs2, bias2, w2, b2, kind2
         raise ValueError(f"tab1 must be {(B, table_channels(C), 4)}; got {tuple(tab1.shape)}")
     _affine(w2, b2, C, "resblock3d_fused")
     s1 = scratch.take((ns, C, H, W))
-    circ = 1 if circular else 0
+    circ = 1 if wrap_d else 0
     N.check(N.lib().ds_volume_to_slices_act(_p(s1), _p(h.contiguous()), _p(tab1), B, C, D, H * W, circ, _stream()),
             "ds_volume_to_slices_act")
     s2 = scratch.take((ns, C, H, W))
-    if not circular:
+    if not wrap_d:
         s2[0].zero_()                                       # the outermost pad slices are never written by the launches
         s2[ns - 1].zero_()
     ts = scratch.take((ns - 2, C, conv_tile_count(H, W), 4))
     rows = _slice_rows(shift, B, D, C, scratch)
-    _depth_taps(s1, s2, packs1, bias1, rows, N.DS_LOAD_PLAIN, bool(circular), tile_stats=ts, in_amax=NORMALISED)   # S1 = SiLU(norm1(h))
-    if circular:
+    _depth_taps(s1, s2, packs1, bias1, rows, N.DS_LOAD_PLAIN, plane, tile_stats=ts, in_amax=NORMALISED)   # S1 = SiLU(norm1(h))
+    if wrap_d:
         N.check(N.lib().ds_wrap_pad_slices(_p(s2), B, C, D, H * W, _stream()), "ds_wrap_pad_slices")
     tab2 = scratch.take((ns, table_channels(C), 4))
     N.check(N.lib().ds_slice_tables(_p(tab2), _p(ts), _p(w2), _p(b2), B, C, D, ts.shape[2], D * H * W, float(eps), int(kind2),
                                     circ, _stream()), "ds_slice_tables")
-    _depth_taps(s2, s1, packs2, bias2, None, N.DS_LOAD_PLAIN, bool(circular), prenorm=tab2)  # S1 is dead: reuse it for S3
+    _depth_taps(s2, s1, packs2, bias2, None, N.DS_LOAD_PLAIN, plane, prenorm=tab2)  # S1 is dead: reuse it for S3
     _from_slices(out, s1, h, res2, B, C, D, H * W, out_stats)
     scratch.give()
     return out
@@ -695,7 +721,9 @@ def conv3d_mfma(x, packs, bias=None, shift=None, res1=None, res2=None, load_mode
     the two slice copies, so that a captured loop allocates nothing.  out_stats: [B, Cout, volume_stat_tiles(D, H*W), 4],
     filled with the result's shifted partial sums (the consumer's norm table, ds_inorm_table with count D*H*W).
     in_amax: NORMALISED for a norm + SiLU output; otherwise the per-slice activation exponents are taken from a reduction over the
-    slice copy (in a pool buffer when ws is given)."""
+    slice copy (in a pool buffer when ws is given).  circular: False, True or (D, H, W) flags (circular_axes): the depth flag fills
+    the pad slices with wrapped neighbours instead of zeros, the other two go to the 2-D launches."""
+    wrap_d, *plane = circular_axes(circular, 3)
     require_device(x, "x")
     B, Cin, Din, Hi, Wi = x.shape
     Cout = packs[0].Cout
@@ -704,17 +732,17 @@ def conv3d_mfma(x, packs, bias=None, shift=None, res1=None, res2=None, load_mode
     out = _out(out, (B, Cout, D, H, W), x)
     _residuals((B, Cout, D, H, W), res1, res2)
     P = len(packs) // 2
-    if circular and P > D:
+    if wrap_d and P > D:
         raise ValueError(f"periodic padding of {P} slices needs a depth of at least {P}; got {D}")
     ns, scratch = B * (D + 2 * P), _Scratch(ws, x.device)
     s_in = scratch.take((ns, Cin, Hi, Wi))
-    N.check(N.lib().ds_volume_to_slices(_p(s_in), _p(x.contiguous()), B, Cin, D, Hi * Wi, depth_mode, 1 if circular else 0, P,
+    N.check(N.lib().ds_volume_to_slices(_p(s_in), _p(x.contiguous()), B, Cin, D, Hi * Wi, depth_mode, 1 if wrap_d else 0, P,
                                         _stream()), "ds_volume_to_slices")
     s_out = scratch.take((ns, Cout, H, W))
     rows = _slice_rows(shift, B, D, Cout, scratch, pad=P)
     if in_amax is not NORMALISED:
         in_amax = absmax_rows(s_in, out=scratch.amax(ns))
-    _depth_taps(s_in, s_out, packs, bias, rows, load_mode, circular, in_amax=in_amax)
+    _depth_taps(s_in, s_out, packs, bias, rows, load_mode, tuple(plane), in_amax=in_amax)
     _from_slices(out, s_out, res1, res2, B, Cout, D, H * W, out_stats, pad=P)
     scratch.give()
     return out
@@ -1107,15 +1135,17 @@ def conv(x, pw, **kw):
 
 
 def conv_direct(x, w, bias=None, circular=False, out=None):
-    """3x3 'same' convolution with Cout <= 4, exact fp32, raw torch weight layout (output layers)."""
+    """3x3 'same' convolution with Cout <= 4, exact fp32, raw torch weight layout (output layers).  circular: False, True
+    or (H, W) flags (circular_axes)."""
+    pad = pad_word(circular, 2)
     B, Cin, H, W = x.shape
     Cout = w.shape[0]
     if tuple(w.shape) != (Cout, Cin, 3, 3):
         raise ValueError("conv_direct: weight must be [Cout, Cin, 3, 3]")
     out = _out(out, (B, Cout, H, W), x)
     _entries(bias, Cout, "bias must have Cout entries")
-    N.check(N.lib().ds_conv2d_direct(_p(out), _p(x), _p(w), _p(bias), B, Cin, Cout, H, W, 1 if circular else 0,
-                                     _stream()), "ds_conv2d_direct")
+    N.check(N.lib().ds_conv2d_direct(_p(out), _p(x), _p(w), _p(bias), B, Cin, Cout, H, W,
+                                     (pad & ~N.DS_PAD_CIRCULAR) | 1 if pad else 0, _stream()), "ds_conv2d_direct")
     return out
 
 
@@ -1391,7 +1421,8 @@ def conv2d(x, w_packed, Cout, ks, bias=None, shift=None, res1=None, res2=None,
     per-sample max |out| for the next raw-input launch; amax_split (fp16x3 1x1 only): out_amax is [2, B] and channels >=
     amax_split report to its second row (the attention in-projection: q, k | v).
     fp16x3 3x3, plain load only (ds_conv2d_h3_pc): pool = PoolOut that may receive MaxPool2d(2) of the result; pc_raw: a launch
-    without prenorm may take the persistent kernel."""
+    without prenorm may take the persistent kernel.  circular: False, True or (H, W) flags (circular_axes)."""
+    pad = pad_word(circular, 2)
     B, Cin, Hin, Win = x.shape
     H, W = _load_sides(load_mode, (Hin, Win))
     if pool is not None:
@@ -1422,7 +1453,7 @@ def conv2d(x, w_packed, Cout, ks, bias=None, shift=None, res1=None, res2=None,
         pout = _pi(out_amax, 2 * B if amax_split else B, "out_amax")
     elif out_amax is not None:
         raise ValueError("out_amax is a feature of the fp16x3 kernels (use absmax_rows on the result)")
-    if circular and ks == 3 and kind != "fp16x3":
+    if pad and ks == 3 and kind != "fp16x3":
         raise NotImplementedError("periodic padding is implemented in the fp16x3 convolution only")
     if prenorm is not None and (ks != 3 or tuple(prenorm.shape) != (B, table_channels(Cin), 4)):
         raise ValueError(f"prenorm must be [B, ceil16(Cin), 4] on a 3x3 convolution; got {tuple(prenorm.shape)}")
@@ -1444,7 +1475,7 @@ def conv2d(x, w_packed, Cout, ks, bias=None, shift=None, res1=None, res2=None,
             raise ValueError("w_up size does not match (Cout, Cin)")
         N.check(N.lib().ds_conv2d_h3_up(_p(out), _p(x), _p(w_up), int(up_wshift), _p(bias), _p(shift), stride,
                                         _p(res1), _p(res2), B, Cin, Cout, Hin, Win,
-                                        (N.DS_PAD_CIRCULAR if circular else 0) | (N.DS_RES1_UPSAMPLED if res1_upsampled else 0),
+                                        pad | (N.DS_RES1_UPSAMPLED if res1_upsampled else 0),
                                         _p(prenorm), _p(tile_stats), pin, pout, _stream()), "ds_conv2d_h3_up")
     elif kind == "fp16x3" and (pool is not None or pc_raw):
         if load_mode != N.DS_LOAD_PLAIN:
@@ -1453,7 +1484,7 @@ def conv2d(x, w_packed, Cout, ks, bias=None, shift=None, res1=None, res2=None,
         did = ctypes.c_int(0)
         N.check(N.lib().ds_conv2d_h3_pc(_p(out), _p(x), _p(w_packed), int(wshift), _p(bias), _p(shift), stride,
                                         _p(res1), _p(res2), B, Cin, Cout, H, W,
-                                        tap | (N.DS_PAD_CIRCULAR if circular else 0) | (N.DS_RES1_UPSAMPLED if res1_upsampled else 0),
+                                        tap | pad | (N.DS_RES1_UPSAMPLED if res1_upsampled else 0),
                                         _p(prenorm), _p(tile_stats), pin, pout, _stream(), _p(pp), ctypes.byref(did),
                                         N.DS_PC_RAW if pc_raw else 0), "ds_conv2d_h3_pc")
         if pool is not None:
@@ -1461,7 +1492,7 @@ def conv2d(x, w_packed, Cout, ks, bias=None, shift=None, res1=None, res2=None,
     elif kind == "fp16x3":
         N.check(N.lib().ds_conv2d_h3(_p(out), _p(x), _p(w_packed), int(wshift), _p(bias), _p(shift), stride,
                                      _p(res1), _p(res2), B, Cin, Cout, H, W,
-                                     load_mode | tap | (N.DS_PAD_CIRCULAR if circular else 0) | (N.DS_RES1_UPSAMPLED if res1_upsampled else 0),
+                                     load_mode | tap | pad | (N.DS_RES1_UPSAMPLED if res1_upsampled else 0),
                                      _p(prenorm), _p(tile_stats), pin, pout,
                                      _stream()), "ds_conv2d_h3")
     elif kind == "bf16x6":

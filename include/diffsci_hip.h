@@ -182,7 +182,12 @@ enum { DS_LOAD_PLAIN = 0, DS_LOAD_MAXPOOL2 = 1, DS_LOAD_UPSAMPLE2 = 2, DS_LOAD_A
        DS_RES1_UPSAMPLED = 32 /* OR-ed into load_mode of ds_conv2d_h3: res1 is [B, Cout, H/2, W/2] and is added
                                  nearest-upsampled -- ADM's convresidual(upsample(x)) = upsample(convresidual(x)), adm.py:345-349 */,
        DS_PAD_CIRCULAR = 16 /* OR-ed into load_mode of ds_conv2d_h3: periodic instead of zero padding in H and W
-                               (CircularConv2d, commonlayers.py:918-971; applied to the pooled / upsampled image) */ };
+                               (CircularConv2d, commonlayers.py:918-971; applied to the pooled / upsampled image) */,
+       /* circular_dims of CircularConv2d / CircularConv3d: together with DS_PAD_CIRCULAR, "this axis is zero-padded instead".
+        * DS_PAD_CIRCULAR alone stays "every axis"; at least one axis must stay periodic, DS_PAD_ZERO_D is for volumes
+        * (ds_conv3d_direct) only, and any of the three without DS_PAD_CIRCULAR is DS_ERR_UNSUPPORTED.  The `circular` ints of
+        * ds_conv2d_direct take the same bits beside 1: 0, or 1 | subset of (DS_PAD_ZERO_H, DS_PAD_ZERO_W). */
+       DS_PAD_ZERO_H = 64, DS_PAD_ZERO_W = 128, DS_PAD_ZERO_D = 0x10000 };
 /* OR-ed into load_mode of ds_conv2d_h3: the 3x3 window is centred at (y + oy, x + ox) instead of (y, x), -8 <= oy, ox <= 7
  * (in the coordinates of the pooled / upsampled image; zero padding).  A k x k kernel with k = 5, 7, ... (kernel_size /
  * in_out_kernel_size / transition_kernel_size of PUNetGConfig, punetg_config.py:19-25) is the sum of ceil(k/3)^2 such
@@ -290,8 +295,8 @@ int ds_conv_tile_count(int H, int W);
  * evaluated at the LOW resolution: for each of the four output parities the 3x3 kernel collapses to a 2x2 kernel
  * on the un-upsampled input (taps summed at pack time), 16 instead of 36 multiply-adds per output.  in is
  * [B,Cin,Hl,Wl], out [B,Cout,2Hl,2Wl]; same epilogue terms, prenorm and tile_stats (4 tiles per low-resolution
- * tile: the count equals ds_conv_tile_count(2Hl, 2Wl)) as ds_conv2d_h3.  flags: DS_PAD_CIRCULAR and/or
- * DS_RES1_UPSAMPLED.  Only for inputs that are whole 8x32 or 16x16 tiles (ds_conv2d_h3_up_supported); other
+ * tile: the count equals ds_conv_tile_count(2Hl, 2Wl)) as ds_conv2d_h3.  flags: DS_PAD_CIRCULAR (with DS_PAD_ZERO_H or
+ * DS_PAD_ZERO_W: the other axis only) and/or DS_RES1_UPSAMPLED.  Only for inputs that are whole 8x32 or 16x16 tiles (ds_conv2d_h3_up_supported); other
  * shapes use ds_conv2d_h3 with DS_LOAD_UPSAMPLE2. */
 /* The same convolution with its input given as pre-split fp16 hi / lo IMAGES in the kernel's LDS layout -- what
  * ds_inorm_silu_images writes: [B][ceil(Cin/16)][piece 2][half 2][H+2][W+2] 16-byte vectors of 8 channels, zero border (the
@@ -360,7 +365,8 @@ int ds_gnorm1_stats_tiles(float* stats, const float* stats_a, int Ca, int ntiles
 
 /* 3x3 "same" convolution for Cout <= 4 (the networks' output layers: punetg.py:415, adm.py:193-215) as an
  * exact-fp32 FMA chain, streaming the input once (HBM-bound) instead of padding Cout to a 64-channel MFMA
- * tile.  w: torch layout [Cout, Cin, 3, 3] (no repacking).  circular != 0: periodic padding. */
+ * tile.  w: torch layout [Cout, Cin, 3, 3] (no repacking).  circular: 0 = zero padding, 1 = periodic in H and W,
+ * 1 | DS_PAD_ZERO_H or 1 | DS_PAD_ZERO_W = periodic along the other axis only; anything else DS_ERR_UNSUPPORTED. */
 int ds_conv2d_direct(float* out, const float* in, const float* w, const float* bias, int B, int Cin, int Cout,
                      int H, int W, int circular, void* stream);
 
@@ -368,7 +374,7 @@ int ds_conv2d_direct(float* out, const float* in, const float* w, const float* b
  * MagnitudePreservingConv3d -- commonlayers.py:25-160,973-1040; normedlayers.py:58-92), exact fp32, torch weight
  * layout [Cout,Cin,3,3,3].  load_mode: DS_LOAD_PLAIN, DS_LOAD_MAXPOOL2 (in is [B,Cin,2D,2H,2W]: DownSampler's
  * MaxPool3d(2) in the loader) or DS_LOAD_UPSAMPLE2 (in is [B,Cin,D/2,H/2,W/2]: UpSampler's nearest x2), optionally
- * OR-ed with DS_PAD_CIRCULAR.  out = (((conv + bias[co]) + shift[b,co]) + res1) + res2. */
+ * OR-ed with DS_PAD_CIRCULAR (every axis; with DS_PAD_ZERO_D / _H / _W: not that one).  out = (((conv + bias[co]) + shift[b,co]) + res1) + res2. */
 int ds_conv3d_direct(float* out, const float* in, const float* w, const float* bias, const float* shift,
                      int shift_stride, const float* res1, const float* res2, int B, int Cin, int Cout, int D, int H,
                      int W, int load_mode, void* stream);

@@ -602,6 +602,10 @@ int heads_generic(float* out, const float* qkv, int B, int E, int heads, int L, 
   const size_t lds = (size_t)(d + L) * sizeof(float);
   DS_REQUIRE(lds <= 64 * 1024, DS_ERR_UNSUPPORTED, "ds_attention_heads_generic: d + L = %d is too large for the generic path", d + L);
   if (B == 0) return DS_OK;
+  if (lds > 48 * 1024) {                             // set once, at the cap: the size varies with L
+    const int rc = ds::ensure_dynamic_lds<&k_attn_heads_generic>(64 * 1024, "hipFuncSetAttribute(attn_heads_generic)");
+    if (rc != DS_OK) return rc;
+  }
   const float scale = (float)sqrt(1.0 / (double)d);
   hipLaunchKernelGGL(k_attn_heads_generic, dim3(L, B * heads), dim3(64), lds, s, out, qkv, d, heads, L, scale);
   DS_CHECK_LAUNCH("ds_attention_heads_generic");

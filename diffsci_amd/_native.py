@@ -18,6 +18,8 @@ DS_PAD_ZERO_H, DS_PAD_ZERO_W, DS_PAD_ZERO_D = 64, 128, 0x10000   # with DS_PAD_C
 DS_RES1_UPSAMPLED = 32
 DS_PC_RAW, DS_PC_IMAGES = 1, 2
 DS_SI_BLEND, DS_SI_RENOISE = 1, 2
+DS_DDPM_CLASSICAL, DS_DDPM_GENERALIZED, DS_DDPM_FORWARD = 0, 1, 2          # ds_ddpm_step's flags: form | noise mode
+DS_DDPM_NOISE_NONE, DS_DDPM_NOISE_EPS, DS_DDPM_NOISE_PHILOX = 0, 4, 8
 
 
 class EvalCoef(Structure):
@@ -33,6 +35,11 @@ class SIStep(Structure):
     """struct ds_si_step."""
     _fields_ = [(n, c_float) for n in ("score_a", "score_b", "score_den", "neg_half_omega", "dt", "noise_coef", "patch_alpha",
                                        "patch_sigma", "jump_alpha", "jump_sigma", "c_in_next")]
+
+
+class DDPMCoef(Structure):
+    """struct ds_ddpm_coef."""
+    _fields_ = [(n, c_float) for n in ("c0", "c1", "c2", "c3", "c4")] + [("nonfinite", c_void_p)]
 
 
 class NativeLibraryError(RuntimeError):
@@ -152,6 +159,7 @@ _PROTOS = {
     "ds_si_inpaint_counters": (c_uint64, [c_int, c_size_t, c_int]),
     "ds_si_inpaint_step": (c_int, [_P, _P, _P, _P, _P, POINTER(EvalCoef), POINTER(SIStep), _P, _P, _P, _P, _P, _P, _P, c_uint64,
                                    c_int, c_size_t, _P, c_int]),
+    "ds_ddpm_step": (c_int, [_P, _P, _P, POINTER(DDPMCoef), _P, _P, c_uint64, c_size_t, _P, c_int]),
     # ds_convit.hip: the flags word closes each list
     "ds_channel_rmsnorm": (c_int, [_P, _P, _P, _P, c_int, c_int, c_int, c_int, c_int, c_int, c_float, _P, _P, c_int]),
     "ds_rope2d": (c_int, [_P, _P, c_int, c_int, c_int, c_int, _P, _P, c_int]),

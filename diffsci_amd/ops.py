@@ -455,6 +455,41 @@ def euler(x, f, k, dt, fu=None, x_out=None, xin_out=None, c_in_next=1.0, eps=Non
     return x_out
 
 
+DDPM_FORMS = {"classical": N.DS_DDPM_CLASSICAL, "generalized": N.DS_DDPM_GENERALIZED, "forward": N.DS_DDPM_FORWARD}
+
+
+def ddpm_step(x, f, k, form, eps=None, philox=None, out=None):
+    """One DDPM / DDIM step (ds_ddpm.hip) under k (DDPMCoef): form "classical" c1*(x - c0*f) + c2*e, "generalized"
+    (c2*((x - f*c0)/c1) + c3*f) + c4*e, or "forward" c0*x + c1*e (f is None).  e: eps (injected, x's extent), philox = (state,
+    offset) (drawn in the kernel), or neither -- the noise term is then dropped.  out: x itself (in place), or any other buffer of
+    x's shape (a history row); default a new tensor.  ValueError / TypeError before any launch for what a kernel would overrun or
+    misread."""
+    if form not in DDPM_FORMS:
+        raise ValueError(f"ddpm_step: form must be one of {sorted(DDPM_FORMS)}; got {form!r}")
+    if not isinstance(k, N.DDPMCoef):
+        raise TypeError("ddpm_step: k must be a DDPMCoef")
+    require_device(x, "x")
+    if form == "forward":
+        if f is not None:
+            raise ValueError("ddpm_step: the forward form reads no network output (f must be None)")
+    elif f is None:
+        raise ValueError(f"ddpm_step: the {form} form reads the network output f")
+    if eps is not None and philox is not None:
+        raise ValueError("ddpm_step: give injected eps or a Philox state, not both")
+    out = _out(out, x.shape, x)
+    n = _same_numel(x, f, eps, out)
+    if out.data_ptr() != x.data_ptr() and _overlap(out, x):
+        raise ValueError("ddpm_step: out overlaps x (it may only be x itself)")
+    if any(_overlap(out, t) for t in (f, eps)):
+        raise ValueError("ddpm_step: out overlaps an input")
+    ps, po = _philox(philox)
+    flags = DDPM_FORMS[form] | (N.DS_DDPM_NOISE_EPS if eps is not None else N.DS_DDPM_NOISE_PHILOX if ps is not None
+                                else N.DS_DDPM_NOISE_NONE)
+    N.check(N.lib().ds_ddpm_step(_p(out, "out"), _p(x, "x"), _p(f, "f"), ctypes.byref(k), _p(eps, "eps"), ps, po, n, _stream(),
+                                 flags), "ds_ddpm_step")
+    return out
+
+
 def _overlap(a, b):
     """Do two tensors share bytes?  (contiguous tensors: their address ranges)"""
     if a is None or b is None or not a.numel() or not b.numel():

@@ -725,6 +725,29 @@ int ds_si_inpaint_step(float* x_out, float* xin_out, const float* x, const float
                        int B, size_t n_per_sample, void* stream, int flags);
 
 /* ------------------------------------------------------------------------------------
+ * The discrete DDPM / DDIM step (ddpm/v2/integrators.py), ds_ddpm.hip: one pass over n fp32 elements, x_out may alias x or point
+ * anywhere else (a history row).  flags = form | noise mode.  Each scalar is one fp32 value computed on the host; the arithmetic is
+ * the reference's, in its order, one rounding per operation:
+ *   DS_DDPM_CLASSICAL    r = c1*(x - c0*f) + c2*e            c0 = beta/sqrt(1 - calpha), c1 = 1/sqrt(alpha), c2 = sigma_t
+ *   DS_DDPM_GENERALIZED  x0 = (x - f*c0)/c1;  r = (c2*x0 + c3*f) + c4*e
+ *                        c0 = sqrt(1 - calpha), c1 = sqrt(calpha), c2 = sqrt(calpha_prev), c3 = sqrt(relu(1 - calpha_prev - sigma_t^2)),
+ *                        c4 = sigma_t
+ *   DS_DDPM_FORWARD      r = c0*x + c1*e                     (f is not read and may be NULL)
+ * Noise: DS_DDPM_NOISE_NONE drops the last term (sigma_t = 0: DDIM); DS_DDPM_NOISE_EPS reads e from eps [n];
+ * DS_DDPM_NOISE_PHILOX draws it from ds_philox_normal's stream of philox_state (device memory, (seed, base)) at philox_offset.
+ * eps / philox_state must be NULL in the modes that do not read them.  nonfinite as ds_eval_coef's: when not NULL the word is
+ * raised if x_out holds inf / NaN.  n % 4 == 0 and 16-byte aligned pointers take 16-byte accesses, anything else the
+ * element-wise path. */
+typedef struct ds_ddpm_coef {
+  float c0, c1, c2, c3, c4;
+  uint32_t* nonfinite;
+} ds_ddpm_coef;
+enum { DS_DDPM_CLASSICAL = 0, DS_DDPM_GENERALIZED = 1, DS_DDPM_FORWARD = 2, DS_DDPM_FORM_MASK = 3,
+       DS_DDPM_NOISE_NONE = 0, DS_DDPM_NOISE_EPS = 4, DS_DDPM_NOISE_PHILOX = 8, DS_DDPM_NOISE_MASK = 12 };
+int ds_ddpm_step(float* x_out, const float* x, const float* f, const ds_ddpm_coef* k, const float* eps,
+                 const uint64_t* philox_state, uint64_t philox_offset, size_t n, void* stream, int flags);
+
+/* ------------------------------------------------------------------------------------
  * Streaming layers of the ConVit score network (convit.py), ds_convit.hip.  Tensors are fp32
  * [B, E, H, W]; the per-sample maxima (out_amax: optional int32 slots holding float bits,
  * zeroed or merged into) serve the fp16x3 launch that reads the result.  No allocation, no

@@ -18,9 +18,8 @@ Quirks of the reference that are kept: ``sample`` concatenates its minibatches a
 import torch
 
 from .... import ops
-from ...karras.engine import ModuleSource, PlanCache, condition_signature, model_signature
+from ...karras.engine import ModuleSource, PlanCache, guarded_run
 from ...karras.karrasmodule import dict_unsqueeze, get_minibatch_sizes
-from ...nets import precision
 from . import integrators, schedulers
 from .steploop import DDPMLoop
 
@@ -131,30 +130,9 @@ class DDPMModule(torch.nn.Module):
             return integ.propagate_backward(x, rhs, nsteps=nsteps, record_history=record_history, **kw)
         T = integ.scheduler.T if nsteps is None else nsteps
         table = integ.backward_table(T)
-        injected = eps is not None
-        if injected and (eps.shape[0] < len(table.rows) or tuple(eps.shape[1:]) != tuple(x.shape)):
+        if eps is not None and (eps.shape[0] < len(table.rows) or tuple(eps.shape[1:]) != tuple(x.shape)):
             raise ValueError(f"eps must be [nsteps = {len(table.rows)}, *x.shape]; got {tuple(eps.shape)}")
-        checked = [False]
-
-        def run():
-            src = ModuleSource(self, y, 1.0, x.shape[0], x)
-            checked[0] = src.nonfinite_word is not None and len(table.rows) > 0      # the last step kernel looks at the result
-
-            def make_loop():
-                return DDPMLoop(table, src, x, record_history, injected_noise=injected, noise_shard=self.noise_shard)
-
-            if self.use_graph and x.is_cuda and src.planned and len(table.rows) > 0:
-                key = (tuple(x.shape), str(x.device), T, record_history, table.kind, injected, condition_signature(y),
-                       self.noise_shard, table.digest(), model_signature(self.model))
-                return self._plans.run(key, make_loop, x, y=y, eps=eps)
-            loop = make_loop()
-            loop.load(x)
-            loop.set_noise(eps)
-            loop.launch()
-            return loop.result()
-
-        out = run()
-        if precision.needs_escalation(self.model, out, x, result_checked=checked[0]):     # see nets/precision.py
-            precision.escalate(self.model)
-            out = run()
-        return out
+        # only a planned network is captured (no capture_eager here), and never a run of no steps
+        return guarded_run(self._plans, self.model, lambda: ModuleSource(self, y, 1.0, x.shape[0], x), DDPMLoop, table, x, y=y,
+                           eps=eps, use_graph=self.use_graph and len(table.rows) > 0, extras=(T,),
+                           record_history=record_history, noise_shard=self.noise_shard)

@@ -53,12 +53,8 @@ class Integrator(torch.nn.Module):
         ops.require_device(x, "x")
         if eps is not None and (eps.shape[0] < len(table.rows) or tuple(eps.shape[1:]) != tuple(x.shape)):
             raise ValueError(f"eps must be [nsteps = {len(table.rows)}, *x.shape]; got {tuple(eps.shape)}")
-        loop = DDPMLoop(table, ScoreFnSource(noise_predictor, x.shape[0], x), x, record_history,
-                        injected_noise=eps is not None, noise_shard=noise_shard)
-        loop.load(x)
-        loop.set_noise(eps)
-        loop.launch()
-        return loop.result()
+        return DDPMLoop(table, ScoreFnSource(noise_predictor, x.shape[0], x), x, record_history,
+                        injected_noise=eps is not None, noise_shard=noise_shard).run(x, eps=eps)
 
     def _one(self, x, table, noise_predictor, eps):
         return self._run(x, table, noise_predictor, False, None if eps is None else eps[None])

@@ -5,8 +5,8 @@ per run on the CPU, in fp32, by calling the scheduler and the integrator's ``noi
 reference's own operation sequence (integrators.py:91-107, 116-122, 197-225), so the numbers handed to the kernel are
 bit-identical to the ones the reference's CPU path broadcasts over the state.
 
-The loop is engine.Loop with another launch sequence: buffers, the Philox device state, ``noise_shard`` addressing, ``load`` /
-``set_noise`` / ``result`` are inherited, so engine.PlanCache captures and replays it like a Karras run.  Per step: one
+The loop is an engine.StepNoiseLoop -- the state or the history, one draw per step, ``noise_shard`` addressing and the run
+protocol are the base's -- with its own launch sequence and no buffer of its own; engine.PlanCache captures and replays it.  Per step: one
 evaluation through the source -- the network reads the state itself, there is no c_in*x copy -- and one ds_ddpm_step:
 read x, read F, write x'.  A row speaks the sources' vocabulary: ``sigma`` and ``c_noise`` are the time handed to the
 network (engine.ScoreFnSource passes sigma*ones(B), engine.ModuleSource tabulates embed_time(c_noise))."""
@@ -17,7 +17,7 @@ import torch
 
 from .... import ops
 from ...._native import DDPMCoef
-from ...karras.engine import Loop
+from ...karras.engine import StepNoiseLoop
 
 NOISE_SLOT = {"classical": 2, "generalized": 4, "forward": 1}       # which coefficient multiplies the draw
 
@@ -106,13 +106,11 @@ def forward_table(integrator, T, form, times=None):
     return DDPMTable("ddpm-forward", rows)
 
 
-class DDPMLoop(Loop):
-    """Usage as engine.Loop: load(x0); set_noise(eps); launch(); result().  eps [nsteps, *shape] holds one draw per step in
-    the order of the reference's randn_like calls (it draws at every step, also where sigma_t = 0)."""
-
-    def __init__(self, table: DDPMTable, source, like, record_history=False, injected_noise=False, noise_shard=None):
-        super().__init__(table, source, like, record_history, injected_noise=injected_noise, noise_shard=noise_shard)
-        self.xin = self.tmp = self.tmp2 = None            # the evaluation reads the state; the step needs no scratch
+class DDPMLoop(StepNoiseLoop):
+    """DDPMLoop(table, source, like, record_history=False, injected_noise=False, noise_shard=None); load(x0); set_noise(eps);
+    launch(); result().  eps [nsteps, *shape] holds one draw per step in the order of the reference's randn_like calls (it
+    draws at every step, also where sigma_t = 0)."""
+    xin = tmp = tmp2 = None                               # the evaluation reads the state; the step needs no scratch
 
     def launch(self, max_rows=None):
         rows, source = self.table.rows, self.source

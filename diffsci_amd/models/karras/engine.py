@@ -278,38 +278,105 @@ def device_generator_state(device, counters):
     return seed, offset
 
 
-class Loop:
-    """Buffers + launch sequence of one tabulated run.  Construction allocates everything and lets
-    the source precompute its per-evaluation tables; ``launch`` only enqueues kernels (plus
-    whatever the source's evaluation does), so for a planned ModuleSource it can be captured into
-    a hipGraph and replayed.
+class LoopBase:
+    """What every tabulated run has, whatever its launch sequence: the state (or the history, whose row 0 is the state), the
+    range guard's word, the source's per-evaluation tables, the noise plumbing both modes share, and the protocol
 
-    Noise of the stochastic integrators (reference: one torch.randn_like(x) per step, integrators.py:66-69,103-104):
-      injected_noise=True   eps [nsteps, *shape] supplied by the caller (parity runs replay the reference's draws);
-      injected_noise=False  generated inside the churn / Euler-Maruyama kernels by Philox from a 16-byte device
-                            state (seed, base offset) that set_noise() rewrites -- no eps buffer, graph-capturable.
+        loop.load(x0[, scale]); loop.set_inputs(*inputs); loop.set_noise(eps); loop.launch(); loop.result()
 
-    Usage: loop.load(x0[, scale]); loop.set_noise(eps); loop.launch(); loop.result()."""
+    which ``run`` spells once.  Construction allocates everything and lets the source precompute its tables; ``launch`` only
+    enqueues kernels (plus whatever the source's evaluation does), so for a planned ModuleSource it can be captured into a
+    hipGraph and replayed (PlanCache).
 
-    def __init__(self, table: StepTable, source, like, record_history=False, injected_noise=False, noise_shard=None):
+    A family (Loop, siloop.SILoop, ddpm.v2.steploop.DDPMLoop) adds the buffers its own launch sequence reads, ``launch(max_rows)``
+    -- max_rows: only the first rows, the warm-up before a capture -- and what is its own about noise: either ``eps`` (the
+    buffers injected draws are copied into, by ``_copy_eps``) or ``rng`` (``_make_rng()``: the 16-byte Philox device state
+    (seed, base offset) the kernels read, no eps buffer, graph-capturable), and ``noise_counters``, the Philox counters one run
+    consumes.  A run without noise has neither."""
+    noise_counters = 0
+
+    def __init__(self, table, source, like, record_history=False):
         ops.require_device(like, "x")
         self.table, self.source, self.record_history = table, source, record_history
-        n = len(table.rows)
-        shape, dev = tuple(like.shape), like.device
-        new = lambda: torch.empty(shape, dtype=torch.float32, device=dev)  # noqa: E731
+        self.shape, self.device = tuple(like.shape), like.device
         if record_history:
-            self.history = torch.zeros((n + 1,) + shape, dtype=torch.float32, device=dev)   # schedulers.py:68-69
+            self.history = torch.zeros((len(table.rows) + 1,) + self.shape, dtype=torch.float32, device=self.device)   # schedulers.py:68-69
             self.x = self.history[0]
         else:
             self.history = None
-            self.x = new()
-        copies = getattr(source, "xin_copies", 1)
+            self.x = self._new(self.shape)
+        self._final = self.x
         self.nonfinite_word = getattr(source, "nonfinite_word", None)
-        self.xin = (new() if copies == 1 else torch.empty((copies * shape[0],) + shape[1:], dtype=torch.float32, device=dev)) \
-            if source.wants_xin else None
-        self.tmp = new() if (not source.wants_xin or table.kind == "karras") else None
-        self.tmp2 = new() if (not source.wants_xin and table.kind == "karras") else None
         self.eps = self.rng = None
+        source.prepare(table)
+
+    def _new(self, shape):
+        return torch.empty(shape, dtype=torch.float32, device=self.device)
+
+    def _new_xin(self):
+        """The network input c_in*x the step kernels write: one copy, or the [2B, ...] of batched guidance (ModuleSource)."""
+        copies = getattr(self.source, "xin_copies", 1)
+        return self._new(self.shape if copies == 1 else (copies * self.shape[0],) + self.shape[1:])
+
+    def _xin_copies(self, xin):
+        copies = getattr(self.source, "xin_copies", 1)
+        return xin.view((copies,) + self.shape) if copies > 1 else (xin,)
+
+    def _make_rng(self):
+        self.rng = torch.zeros(2, dtype=torch.int64, device=self.device)
+
+    def load(self, x0, scale=None):
+        """state <- x0 (or scale*x0: x*maximum_scale of karrasmodule.py:881)."""
+        ops.require_device(x0, "x")
+        x0 = x0.contiguous()
+        if tuple(x0.shape) != self.shape:
+            raise ValueError("x shape does not match the loop")
+        if scale is None:
+            self.x.copy_(x0)
+        else:
+            ops.scale(x0, scale, out=self.x)
+
+    def set_inputs(self, *inputs):
+        """Further per-run tensors of a loop that has them (siloop.SILoop: x_orig, mask), handed over wherever x is loaded."""
+
+    def set_noise(self, eps=None, seed_offset=None):
+        """Injected mode: eps is copied in (the family checks it).  Generator mode: (seed, offset) -- given, or taken from (and
+        advancing) torch's CUDA generator -- is written to the device state the kernels read."""
+        if self.eps is None and self.rng is None:
+            return
+        if self.eps is not None:
+            if eps is None:
+                raise ValueError("this loop was built for injected noise: pass its draws")
+            self._copy_eps(eps)
+            return
+        if eps is not None:
+            raise ValueError("this loop generates its noise in the kernels: build it with injected_noise=True to pass draws")
+        if seed_offset is None:
+            seed_offset = device_generator_state(self.device, self.noise_counters)
+        seed, offset = seed_offset
+        self.seed_offset = (int(seed), int(offset))
+        as_i64 = lambda v: v - (1 << 64) if v >= (1 << 63) else v      # noqa: E731  (uint64 bit pattern in an int64 tensor)
+        self.rng.copy_(torch.tensor([as_i64(int(seed) & (2**64 - 1)), as_i64(int(offset) & (2**64 - 1))], dtype=torch.int64))
+
+    def run(self, x, scale=None, eps=None, inputs=()):
+        """One eager pass from x: the final state or the history [len(rows)+1, *x.shape] (loop-owned buffers)."""
+        self.load(x, scale)
+        self.set_inputs(*inputs)
+        self.set_noise(eps)
+        self.launch()
+        return self.result()
+
+    def result(self):
+        return self.history if self.record_history else self._final
+
+
+class StepNoiseLoop(LoopBase):
+    """A loop whose rows draw at most one state-shaped eps each (reference: one torch.randn_like(x) per step,
+    integrators.py:66-69,103-104): injected eps is [nsteps, *shape]; generated, step i reads counters
+    i * counters_per_step + noise_base."""
+
+    def __init__(self, table, source, like, record_history=False, injected_noise=False, noise_shard=None):
+        super().__init__(table, source, like, record_history)
         # noise_shard = (first element, total elements): this state is rows [lo, hi) of a larger batch sampled by several
         # ranks (parallel.sample_sharded).  The in-kernel stream is then addressed as the single process would address it --
         # element e of step i reads counter base + i * ceil(total / 4) + (first + e) / 4 -- so the shards of a stochastic
@@ -317,53 +384,38 @@ class Loop:
         first, total = (0, like.numel()) if noise_shard is None else (int(noise_shard[0]), int(noise_shard[1]))
         if first % 4 or first < 0 or first + like.numel() > total:
             raise ValueError("noise_shard: the shard must start at a multiple of 4 elements and lie inside the total")
+        n = len(table.rows)
         self.counters_per_step = ops.philox_counters(total)
         self.noise_base = first // 4
+        self.noise_counters = n * self.counters_per_step
         if table.needs_noise:
             if injected_noise:
-                self.eps = torch.empty((n,) + shape, dtype=torch.float32, device=dev)
+                self.eps = self._new((n,) + self.shape)
             else:
-                self.rng = torch.zeros(2, dtype=torch.int64, device=dev)
-        source.prepare(table)
+                self._make_rng()
 
-    def load(self, x0, scale=None):
-        """state <- x0 (or scale*x0: x*maximum_scale of karrasmodule.py:881)."""
-        ops.require_device(x0, "x")
-        x0 = x0.contiguous()
-        if tuple(x0.shape) != tuple(self.x.shape):
-            raise ValueError("x shape does not match the loop")
-        if scale is None:
-            self.x.copy_(x0)
-        else:
-            ops.scale(x0, scale, out=self.x)
-
-    def set_noise(self, eps=None, seed_offset=None):
-        """Injected mode: eps [>= nsteps, *shape] is copied in.  Generator mode: (seed, offset) -- given, or taken from
-        (and advancing) torch's CUDA generator -- is written to the device state the kernels read."""
-        if not self.table.needs_noise:
-            return
+    def _copy_eps(self, eps):
         n = len(self.table.rows)
-        if self.eps is not None:
-            if eps is None:
-                raise ValueError("this loop was built for injected noise: pass eps [nsteps, *x.shape]")
-            if eps.shape[0] < n or tuple(eps.shape[1:]) != tuple(self.eps.shape[1:]):
-                raise ValueError("eps must be [nsteps, *x.shape]")
-            self.eps.copy_(eps[:n])
-            return
-        if eps is not None:
-            raise ValueError("this loop generates its noise in the kernels: build it with injected_noise=True to pass eps")
-        if seed_offset is None:
-            seed_offset = device_generator_state(self.x.device, n * self.counters_per_step)
-        seed, offset = seed_offset
-        self.seed_offset = (int(seed), int(offset))
-        as_i64 = lambda v: v - (1 << 64) if v >= (1 << 63) else v      # noqa: E731  (uint64 bit pattern in an int64 tensor)
-        self.rng.copy_(torch.tensor([as_i64(int(seed) & (2**64 - 1)), as_i64(int(offset) & (2**64 - 1))], dtype=torch.int64))
+        if eps.shape[0] < n or tuple(eps.shape[1:]) != self.shape:
+            raise ValueError("eps must be [nsteps, *x.shape]")
+        self.eps.copy_(eps[:n])
 
     def step_noise(self, i):
         """The eps of step i as a tensor (generator mode regenerates it from the counters: tests / diagnostics)."""
         if self.eps is not None:
             return self.eps[i]
         return ops.philox_normal(self.rng, i * self.counters_per_step + self.noise_base, self.x.shape)
+
+
+class Loop(StepNoiseLoop):
+    """The Karras launch sequence: Euler, Heun, Euler-Maruyama and the churned Heun of integrators.py, the state read 2x and
+    written 1x per Heun step (the module docstring)."""
+
+    def __init__(self, table: StepTable, source, like, record_history=False, injected_noise=False, noise_shard=None):
+        super().__init__(table, source, like, record_history, injected_noise, noise_shard)
+        self.xin = self._new_xin() if source.wants_xin else None
+        self.tmp = self._new(self.shape) if (not source.wants_xin or table.kind == "karras") else None
+        self.tmp2 = self._new(self.shape) if (not source.wants_xin and table.kind == "karras") else None
 
     def launch(self, max_rows=None):
         """Enqueue the run.  max_rows: only the first rows (the warm-up before a capture: one step touches every buffer the
@@ -379,8 +431,8 @@ class Loop:
         copies = getattr(source, "xin_copies", 1)
         if source.wants_xin and n > 0 and not karras:
             r0 = table.rows[0].first
-            for half in (xin.view((copies,) + tuple(cur.shape)) if copies > 1 else (xin,)):
-                if r0.scaled:                                        # c_in * (x / s): schedulers.py:287, karrasmodule.py:702
+            for half in self._xin_copies(xin):
+                if r0.scaled:                                       # c_in * (x / s): schedulers.py:287, karrasmodule.py:702
                     ops.scale(ops.div_scalar(cur, r0.scale, out=half), r0.c_in, out=half)
                 else:
                     ops.scale(cur, r0.c_in, out=half)                # c_in*x, karrasmodule.py:702
@@ -422,9 +474,6 @@ class Loop:
             cur = nxt
         self._final = cur
 
-    def result(self):
-        return self.history if self.record_history else self._final
-
 
 class _TorchGraph:
     """loop.launch() captured by torch (see PlanCache.run)."""
@@ -452,9 +501,21 @@ class PlanCache:
     def clear(self):
         self.plans = {}
 
-    def run(self, key, make_loop, x, y=None, scale=None, eps=None, torch_graph=False, inputs=None):
-        """inputs: further per-run tensors of a loop that has them (siloop.SILoop: x_orig, mask), handed to loop.set_inputs
-        wherever x is loaded.
+    def lookup(self, key):
+        """The plan of key or None.  Least recently USED goes first: a hit moves the plan to the back."""
+        plan = self.plans.pop(key, None)
+        if plan is not None:
+            self.plans[key] = plan
+        return plan
+
+    def insert(self, key, plan):
+        """At capacity the front entry -- the least recently used -- makes room."""
+        if len(self.plans) >= self.capacity:
+            self.plans.pop(next(iter(self.plans)))
+        self.plans[key] = plan
+
+    def run(self, key, make_loop, x, y=None, scale=None, eps=None, torch_graph=False, inputs=()):
+        """inputs: what loop.set_inputs takes, handed over wherever x is loaded.
         torch_graph: capture with torch.cuda.CUDAGraph instead of ops.Graph -- torch's allocator then serves allocations made
         inside the captured region from a pool the graph owns, which is what a run through user torch modules (extra_residual, an
         evaluated-as-given network) needs; our own capture refuses allocations instead (ops.Graph)."""
@@ -463,14 +524,12 @@ class PlanCache:
         caller = torch.cuda.current_stream(x.device)
         self.stream.wait_stream(caller)
         with torch.cuda.stream(self.stream):
-            plan = self.plans.pop(key, None)
-            if plan is not None:
-                self.plans[key] = plan                       # least recently USED goes first: a hit moves the plan to the back
-            if plan is None:
+            plan = self.lookup(key)
+            fresh = plan is None
+            if fresh:
                 loop = make_loop()
                 loop.load(x, scale)
-                if inputs is not None:
-                    loop.set_inputs(*inputs)
+                loop.set_inputs(*inputs)
                 loop.set_noise(eps)
                 # eager warm-up: allocates the workspace, packs the weights, validates shapes.  Two steps, not the run (round 3: the
                 # first call of config 3 took 6.9 s, 3.2 s of them this pass): the first step visits both evaluation slots and every
@@ -488,24 +547,17 @@ class PlanCache:
                     with ops.Graph() as g:
                         loop.launch()
                 plan = (loop, g)
-                if len(self.plans) >= self.capacity:
-                    self.plans.pop(next(iter(self.plans)))
-                self.plans[key] = plan
-                if loop.table.needs_noise and loop.rng is not None:
-                    loop.set_noise(None, seed_offset=loop.seed_offset)    # the replay below repeats the eager pass's draw
-                    replay_same_noise = True
-                else:
-                    replay_same_noise = False
+                self.insert(key, plan)
             else:
-                replay_same_noise = False
                 refresh = getattr(plan[0].source, "refresh", None)
                 if refresh is not None:
                     refresh(y)
             loop, g = plan
             loop.load(x, scale)
-            if inputs is not None:
-                loop.set_inputs(*inputs)
-            if not replay_same_noise:
+            loop.set_inputs(*inputs)
+            if fresh and loop.rng is not None:
+                loop.set_noise(None, seed_offset=loop.seed_offset)    # the replay repeats the warm-up's draw: one advance of the generator per call
+            else:
                 loop.set_noise(eps)
             g.launch()
             out = loop.result().clone()
@@ -513,10 +565,41 @@ class PlanCache:
         return out
 
 
+def plan_key(table, src, x, y, model, injected, loop_args, extras=()):
+    """Everything a capture bakes in.  The common part is assembled here, so no family can leave a component out (a missing one
+    does not crash: it replays a stale graph); a family hands only what is its own as `extras`.  loop_args: the keyword
+    arguments its loop is built with (record_history, noise_shard)."""
+    return (table.kind, src.planned, src.batched_cfg, tuple(x.shape), str(x.device), bool(loop_args.get("record_history", False)),
+            bool(injected), float(src.guidance), condition_signature(y), loop_args.get("noise_shard"), table.digest(),
+            model_signature(model)) + tuple(extras)
+
+
+def guarded_run(plans, model, make_source, loop_cls, table, x, y=None, scale=None, eps=None, inputs=(), use_graph=True,
+                capture_eager=False, extras=(), **loop_args):
+    """One run of `table` from x, as every sampler family does it: build the source, run captured (plans: the module's PlanCache)
+    or eagerly, and when the range guard flags the result (nets/precision.py) escalate the model and run once more, with a new
+    source.  A run is captured when use_graph and x.is_cuda and (the source is planned or capture_eager); a source evaluated
+    as given is then captured by torch and reads a plan-owned condition.  make_source(): the run's source;
+    loop_cls(table, source, x, injected_noise=..., **loop_args): its loop; eps: the injected draws or None."""
+    injected = eps is not None
+
+    def run():
+        src = make_source()
+        checked = src.nonfinite_word is not None and len(table.rows) > 0      # the last step kernel looks at the result
+        make_loop = lambda: loop_cls(table, src, x, injected_noise=injected, **loop_args)     # noqa: E731
+        if use_graph and x.is_cuda and (src.planned or capture_eager):
+            src.static_condition = not src.planned         # evaluated as given: the captured calls read a plan-owned condition
+            key = plan_key(table, src, x, y, model, injected, loop_args, extras)
+            return plans.run(key, make_loop, x, y=y, scale=scale, eps=eps, torch_graph=not src.planned, inputs=inputs), checked
+        return make_loop().run(x, scale, eps, inputs), checked
+
+    out, checked = run()
+    if precision.needs_escalation(model, out, x, result_checked=checked):     # an activation left the fp16x3 range
+        precision.escalate(model)
+        out, _ = run()
+    return out
+
+
 def run_table(table: StepTable, source, x, record_history=False, eps=None):
     """One eager pass: returns the final state (a new tensor) or the history [len(rows)+1, *x.shape]."""
-    loop = Loop(table, source, x, record_history, injected_noise=eps is not None)
-    loop.load(x)
-    loop.set_noise(eps)
-    loop.launch()
-    return loop.result()
+    return Loop(table, source, x, record_history, injected_noise=eps is not None).run(x, eps=eps)

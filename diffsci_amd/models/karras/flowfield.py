@@ -18,9 +18,8 @@ import numpy as np
 import torch
 
 from ... import ops
-from ..nets import precision
 from ..._native import DS_IN_FLOW, DS_IN_NETWORK
-from .engine import Loop, ModuleSource, PlanCache, condition_signature, model_signature
+from .engine import Loop, ModuleSource, PlanCache, guarded_run
 from . import edmbatchnorm
 from .karrasmodule import dict_to, dict_unsqueeze
 from .steptable import EvalRow, StepRow, StepTable
@@ -364,34 +363,17 @@ class SIModule(torch.nn.Module):
         if self.config.preconditioner.generic:
             return self._integrate_generic(x, time_schedule, y, guidance, return_history, integrate_on_sigma, scale)
         table = self._table(time_schedule, integrate_on_sigma)
-
-        checked = [False]
-
-        def run():
-            src = self._source(y, guidance, x)
-            checked[0] = src.nonfinite_word is not None and len(table.rows) > 0      # the last step kernel looks at the result
-            if self.use_graph and x.is_cuda and (src.planned or self.capture_eager):
-                src.static_condition = not src.planned
-                return self._run_planned(table, src, x, y, guidance, return_history, integrate_on_sigma, scale)
-            loop = Loop(table, src, x, return_history)
-            loop.load(x, scale)
-            loop.launch()
-            return loop.result()
-
-        out = run()
-        if precision.needs_escalation(self.model, out, x, result_checked=checked[0]):     # an activation left the fp16x3 range: nets/precision.py
-            precision.escalate(self.model)
-            out = run()
+        out = self._run(Loop, table, x, y, guidance, integrate_on_sigma, scale, record_history=return_history)
         if return_history:                                                        # initial_norm.unnorm, flowfield.py:742-747
             return [(table.t[i].to(x.device), self.initial_norm.unnorm(out[i])) for i in range(out.shape[0])]
         return self.initial_norm.unnorm(out)
 
-    def _run_planned(self, table, src, x, y, guidance, return_history, integrate_on_sigma, scale):
-        """Capture the whole run once per (shape, schedule, guidance, condition structure) and replay it; what depends
-        on the condition's values is refreshed in plan-owned buffers before every replay (engine.PlanCache)."""
-        key = (src.planned, tuple(x.shape), table.digest(), float(guidance), condition_signature(y), bool(return_history),
-               bool(integrate_on_sigma), str(x.device), model_signature(self.model))
-        return self._plans.run(key, lambda: Loop(table, src, x, return_history), x, y=y, scale=scale, torch_graph=not src.planned)
+    def _run(self, loop_cls, table, x, y, guidance, integrate_on_sigma, scale, eps=None, inputs=(), **loop_args):
+        """One guarded run (engine.guarded_run): captured once per plan key and replayed, with what depends on the condition's
+        values refreshed in plan-owned buffers before every replay."""
+        return guarded_run(self._plans, self.model, lambda: self._source(y, guidance, x), loop_cls, table, x, y=y, scale=scale,
+                           eps=eps, inputs=inputs, use_graph=self.use_graph, capture_eager=self.capture_eager,
+                           extras=(bool(integrate_on_sigma),), **loop_args)
 
     def _integrate_generic(self, x, time_schedule, y, guidance, return_history, integrate_on_sigma, scale):
         """integrate_flow_field for preconditioners that cannot be tabulated: Heun steps, the last one Euler
@@ -522,30 +504,7 @@ class SIModule(torch.nn.Module):
         (ds_inpaint.hip), captured once per plan key and replayed with x, the known data, the mask, the condition's values and
         the noise (the draws, or the Philox offset) refreshed.  draws: None (in-kernel Philox seeded from torch's generator) or
         the list of injected draws."""
-        injected = draws is not None
-        checked = [False]
-
-        def run():
-            src = self._source(y, guidance, x)
-            checked[0] = src.nonfinite_word is not None and len(table.rows) > 0
-            make = lambda: siloop.SILoop(table, src, x, injected_noise=injected)     # noqa: E731
-            if self.use_graph and x.is_cuda and (src.planned or self.capture_eager):
-                src.static_condition = not src.planned
-                key = (table.kind, src.planned, tuple(x.shape), table.digest(), float(guidance), condition_signature(y),
-                       bool(integrate_on_sigma), injected, str(x.device), model_signature(self.model))
-                return self._plans.run(key, make, x, y=y, scale=scale, eps=draws, torch_graph=not src.planned, inputs=inputs)
-            loop = make()
-            loop.load(x, scale)
-            loop.set_inputs(*inputs)
-            loop.set_noise(draws)
-            loop.launch()
-            return loop.result()
-
-        out = run()
-        if precision.needs_escalation(self.model, out, x, result_checked=checked[0]):
-            precision.escalate(self.model)
-            out = run()
-        return self.initial_norm.unnorm(out)
+        return self.initial_norm.unnorm(self._run(siloop.SILoop, table, x, y, guidance, integrate_on_sigma, scale, draws, inputs))
 
     @staticmethod
     def _take_draws(noise, table, x_shape):

@@ -16,11 +16,10 @@ from typing import Any
 import torch
 
 from ... import ops
-from ..nets import precision
 from ..._native import DS_IN_NETWORK
 from . import edmbatchnorm, noisesamplers, preconditioners, schedulers
 from .autoregressivesample import LatentSpaceAutoregressive
-from .engine import Loop, ModuleSource, PlanCache, condition_signature, model_signature
+from .engine import Loop, ModuleSource, PlanCache, guarded_run
 from .steptable import build_step_table
 
 
@@ -438,35 +437,11 @@ class KarrasModule(torch.nn.Module, LatentSpaceAutoregressive):
         finally:
             if integrator is not None:
                 sch.unset_temporary_integrator()
-        injected = eps is not None
-
-        checked = [False]
-
-        def run():
-            src = ModuleSource(self, y, guidance, x.shape[0], x)
-            checked[0] = src.nonfinite_word is not None and len(table.rows) > 0      # the last step kernel looks at the result
-
-            def make_loop():
-                return Loop(table, src, x, record_history, injected_noise=injected, noise_shard=self.noise_shard)
-
-            if self.use_graph and x.is_cuda and (src.planned or self.capture_eager):
-                key = (src.planned, src.batched_cfg, tuple(x.shape), str(x.device), nsteps, i0, i1, record_history, table.kind, injected,
-                       (integ.s_schurn, integ.s_tmin, integ.s_tmax, integ.s_noise) if table.kind == "karras" else None,
-                       float(guidance), condition_signature(y), float(sch.langevin_const), repr(sch.langevin_interval), self.noise_shard,
-                       table.digest(), model_signature(self.model))
-                src.static_condition = not src.planned         # evaluated as given: the captured calls read a plan-owned condition
-                return self._plans.run(key, make_loop, x, y=y, scale=scale, eps=eps, torch_graph=not src.planned)
-            loop = make_loop()
-            loop.load(x, scale)
-            loop.set_noise(eps)
-            loop.launch()
-            return loop.result()
-
-        out = run()
-        if precision.needs_escalation(self.model, out, x, result_checked=checked[0]):     # an activation left the fp16x3 range: see nets/precision.py
-            precision.escalate(self.model)
-            out = run()
-        return out
+        extras = (nsteps, i0, i1, (integ.s_schurn, integ.s_tmin, integ.s_tmax, integ.s_noise) if table.kind == "karras" else None,
+                  float(sch.langevin_const), repr(sch.langevin_interval))
+        return guarded_run(self._plans, self.model, lambda: ModuleSource(self, y, guidance, x.shape[0], x), Loop, table, x, y=y,
+                           scale=scale, eps=eps, use_graph=self.use_graph, capture_eager=self.capture_eager, extras=extras,
+                           record_history=record_history, noise_shard=self.noise_shard)
 
     # ---------------------------------------------------------------- encode / decode (non-latent)
     # ---------------------------------------------------------------- inpainting / interpolation

@@ -1,7 +1,7 @@
 """The Euler-Maruyama runs of the stochastic-interpolant sampler on the fused inpainting step (ds_inpaint.hip): the rows of
 SIModule.inpaint (flowfield.py:546-641 of the reference) and of integrate_flow_field(noise_injection=True) (flowfield.py:783-793)
-resolved on the host, and the loop that launches them -- engine.Loop's counterpart, with the same protocol (load, set_noise,
-launch, result), so engine.PlanCache captures and replays it.
+resolved on the host, and the loop that launches them: an engine.LoopBase, which owns the state, the protocol (load, set_inputs,
+set_noise, launch, result) and the Philox state, so engine.PlanCache captures and replays it like any other run.
 
 Per row: one network evaluation through the source, one ds_si_inpaint_step.  The state is updated in place; x_orig, the mask,
 the start noise and the Philox state (or the injected draws) live in buffers the loop owns, rewritten before every replay.
@@ -13,7 +13,7 @@ import torch
 
 from ... import ops
 from ..._native import SIStep
-from .engine import device_generator_state
+from .engine import LoopBase
 from .steptable import EvalRow
 
 
@@ -93,49 +93,32 @@ def em_table(config, time_schedule, integrate_on_sigma=False):
     return SITable(t=ts, rows=[si_row(config, ts[i], ts[i + 1], integrate_on_sigma) for i in range(ts.numel() - 1)])
 
 
-class SILoop:
-    """Buffers + launch sequence of one run of an SITable.  Usage: load(x0[, scale]); set_inputs(x_orig, mask); set_noise(...);
-    launch(); result().
+class SILoop(LoopBase):
+    """The launch sequence of an SITable and the buffers it reads.  Usage: load(x0[, scale]); set_inputs(x_orig, mask);
+    set_noise(...); launch(); result() -- or run(x0, scale, draws, (x_orig, mask)).
 
     Noise: injected_noise=True -- the draws, in the reference's order (per row: the step's [B, *shape], with a blend the patch's
     [1, *shape], with a jump the re-noising [B, *shape] and its patch [1, *shape]), are copied into loop-owned buffers;
-    injected_noise=False -- generated in the kernel from a 16-byte device state, row j at the offset the rows before it consumed
+    injected_noise=False -- generated in the kernel from the device state, row j at the offset the rows before it consumed
     (ds_inpaint.hip)."""
 
     def __init__(self, table: SITable, source, like, injected_noise=False):
-        ops.require_device(like, "x")
-        self.table, self.source = table, source
-        shape, dev = tuple(like.shape), like.device
-        new = lambda s: torch.empty(s, dtype=torch.float32, device=dev)  # noqa: E731
-        self.x = new(shape)
-        copies = getattr(source, "xin_copies", 1)
-        self.xin = new(shape if copies == 1 else (copies * shape[0],) + shape[1:])
+        super().__init__(table, source, like)
+        shape = self.shape
+        self.xin = self._new_xin()
         self.masked = any(r.blend for r in table.rows)
-        self.x_orig = new(shape[1:]) if self.masked else None
-        self.mask = new(shape[1:]) if self.masked else None
-        self.nonfinite_word = getattr(source, "nonfinite_word", None)
+        self.x_orig = self._new(shape[1:]) if self.masked else None
+        self.mask = self._new(shape[1:]) if self.masked else None
         B, n = shape[0], like.numel() // max(shape[0], 1)
         self.offsets, o = [], 0
         for r in table.rows:
             self.offsets.append(o)
             o += ops.si_inpaint_counters(B, n, r.blend, r.jump)
-        self.counters = o
-        self.eps = self.rng = None
+        self.counters = self.noise_counters = o
         if injected_noise:
-            self.eps = [[new(shape if i % 2 == 0 else (1,) + shape[1:]) for i in range(r.draws)] for r in table.rows]
+            self.eps = [[self._new(shape if i % 2 == 0 else (1,) + shape[1:]) for i in range(r.draws)] for r in table.rows]
         else:
-            self.rng = torch.zeros(2, dtype=torch.int64, device=dev)
-        source.prepare(table)
-
-    def load(self, x0, scale=None):
-        ops.require_device(x0, "x")
-        x0 = x0.contiguous()
-        if tuple(x0.shape) != tuple(self.x.shape):
-            raise ValueError("x shape does not match the loop")
-        if scale is None:
-            self.x.copy_(x0)
-        else:
-            ops.scale(x0, scale, out=self.x)
+            self._make_rng()
 
     def set_inputs(self, x_orig=None, mask=None):
         """The known data (network space) and the (soft) mask, [*shape] or [1, *shape]."""
@@ -146,27 +129,15 @@ class SILoop:
                 raise ValueError(f"{what} must hold one sample of shape {tuple(dst.shape)}")
             dst.copy_(src.reshape(dst.shape))
 
-    def set_noise(self, eps=None, seed_offset=None):
-        if self.eps is not None:
-            if eps is None:
-                raise ValueError("this loop was built for injected noise: pass the draws")
-            flat = [b for row in self.eps for b in row]
-            eps = list(eps)
-            if len(eps) < len(flat):
-                raise ValueError(f"the run consumes {len(flat)} draws; got {len(eps)}")
-            for b, e in zip(flat, eps):
-                if tuple(e.shape) != tuple(b.shape):
-                    raise ValueError(f"injected noise has shape {tuple(e.shape)}, expected {tuple(b.shape)}")
-                b.copy_(e)
-            return
-        if eps is not None:
-            raise ValueError("this loop generates its noise in the kernel: build it with injected_noise=True to pass draws")
-        if seed_offset is None:
-            seed_offset = device_generator_state(self.x.device, self.counters)
-        seed, offset = seed_offset
-        self.seed_offset = (int(seed), int(offset))
-        as_i64 = lambda v: v - (1 << 64) if v >= (1 << 63) else v      # noqa: E731  (uint64 bit pattern in an int64 tensor)
-        self.rng.copy_(torch.tensor([as_i64(int(seed) & (2**64 - 1)), as_i64(int(offset) & (2**64 - 1))], dtype=torch.int64))
+    def _copy_eps(self, eps):
+        flat = [b for row in self.eps for b in row]
+        eps = list(eps)
+        if len(eps) < len(flat):
+            raise ValueError(f"the run consumes {len(flat)} draws; got {len(eps)}")
+        for b, e in zip(flat, eps):
+            if tuple(e.shape) != tuple(b.shape):
+                raise ValueError(f"injected noise has shape {tuple(e.shape)}, expected {tuple(b.shape)}")
+            b.copy_(e)
 
     def row_noise(self, j):
         """The draws of row j as tensors (generator mode regenerates them from the counters: tests / diagnostics)."""
@@ -186,7 +157,7 @@ class SILoop:
         x, xin = self.x, self.xin
         copies = getattr(source, "xin_copies", 1)
         if n > 0:
-            for half in (xin.view((copies,) + tuple(x.shape)) if copies > 1 else (xin,)):
+            for half in self._xin_copies(xin):
                 ops.scale(x, rows[0].first.c_in, out=half)
         for j, row in enumerate(rows):
             if max_rows is not None and j >= max_rows:
@@ -199,6 +170,3 @@ class SILoop:
                                 eps=None if self.eps is None else self.eps[j],
                                 philox=None if self.rng is None else (self.rng, self.offsets[j]),
                                 x_out=x, xin_out=xin if nxt is not None else None)
-
-    def result(self):
-        return self.x

@@ -42,10 +42,11 @@ __global__ __launch_bounds__(NT) void k_g1_partial(double* part, const float* __
       const float4* p = reinterpret_cast<const float4*>(src + lo);
       for (size_t k = threadIdx.x; k < n4; k += NT) {
         const float4 v = p[k];
-        const float fs = (v.x + v.y) + (v.z + v.w);
-        const float fq = (v.x * v.x + v.y * v.y) + (v.z * v.z + v.w * v.w);
-        s += (double)fs;
-        q += (double)fq;
+        // widened before they are added or squared, as the scalar path below does: an fp32 square carries an error of
+        // ulp(x^2), which q/n - mean^2 in k_g1_final magnifies by mean^2/var
+        const double x0 = v.x, x1 = v.y, x2 = v.z, x3 = v.w;
+        s += (x0 + x1) + (x2 + x3);
+        q += (x0 * x0 + x1 * x1) + (x2 * x2 + x3 * x3);
       }
       i = lo + n4 * 4;
     }

@@ -3,7 +3,9 @@
 //
 // HBM-bound: 8 bytes per element (one read, one write).  A plane (H*W floats, contiguous in
 // NCHW) is held entirely in registers between the statistics pass and the apply pass:
-//   - planes of <= 1024 floats: one 64-lane wave per plane, reductions by DPP/shuffle only;
+//   - planes of <= 4096 floats: one 64-lane wave per plane (<= 16 float4 per lane), reductions by
+//     DPP/shuffle only -- the planes, the loads and the summation order of k_inorm_images, so the
+//     image form and this one agree bit for bit wherever both exist;
 //   - planes up to 64 Ki floats: one workgroup per plane (256 or 1024 threads, <= 16 float4 per
 //     lane), wave shuffles + one LDS exchange per statistic;
 //   - anything else (H*W not a multiple of 4, or larger): a two-read fallback.
@@ -191,16 +193,16 @@ int launch_inorm(float* out, const float* x, const float* w, const float* b, int
   const float inv = 1.0f / (float)HW;
   const bool vec = (HW % 4 == 0) && ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(out)) & 15u) == 0;
   const int hw4 = HW / 4;
-  if (vec && hw4 <= 256) {
+  if (vec && hw4 <= 1024) {                       // the thresholds of ds_inorm_silu_images: one tree for both forms
     dim3 g((planes + 3) / 4), t(256);
     if (hw4 <= 64) hipLaunchKernelGGL((k_inorm_wave<KIND, 1>), g, t, 0, s, out, x, w, b, planes, C, hw4, inv, eps);
     else if (hw4 <= 128) hipLaunchKernelGGL((k_inorm_wave<KIND, 2>), g, t, 0, s, out, x, w, b, planes, C, hw4, inv, eps);
-    else hipLaunchKernelGGL((k_inorm_wave<KIND, 4>), g, t, 0, s, out, x, w, b, planes, C, hw4, inv, eps);
+    else if (hw4 <= 256) hipLaunchKernelGGL((k_inorm_wave<KIND, 4>), g, t, 0, s, out, x, w, b, planes, C, hw4, inv, eps);
+    else if (hw4 <= 512) hipLaunchKernelGGL((k_inorm_wave<KIND, 8>), g, t, 0, s, out, x, w, b, planes, C, hw4, inv, eps);
+    else hipLaunchKernelGGL((k_inorm_wave<KIND, 16>), g, t, 0, s, out, x, w, b, planes, C, hw4, inv, eps);
   } else if (vec && hw4 <= 4096) {
     dim3 g(planes), t(256);
-    if (hw4 <= 512) hipLaunchKernelGGL((k_inorm_block<KIND, 256, 2>), g, t, 0, s, out, x, w, b, C, hw4, inv, eps);
-    else if (hw4 <= 1024) hipLaunchKernelGGL((k_inorm_block<KIND, 256, 4>), g, t, 0, s, out, x, w, b, C, hw4, inv, eps);
-    else if (hw4 <= 2048) hipLaunchKernelGGL((k_inorm_block<KIND, 256, 8>), g, t, 0, s, out, x, w, b, C, hw4, inv, eps);
+    if (hw4 <= 2048) hipLaunchKernelGGL((k_inorm_block<KIND, 256, 8>), g, t, 0, s, out, x, w, b, C, hw4, inv, eps);
     else hipLaunchKernelGGL((k_inorm_block<KIND, 256, 16>), g, t, 0, s, out, x, w, b, C, hw4, inv, eps);
   } else if (vec && hw4 <= 16384) {
     dim3 g(planes), t(1024);

@@ -305,8 +305,8 @@ int ds_conv_tile_count(int H, int W);
  * padding, no fused norm; Cin must give an even number of 16-channel chunks (DS_ERR_UNSUPPORTED otherwise).  Epilogue terms and
  * tile_stats as ds_conv2d_h3.  Replaces conv(SiLU(norm(x))) of commonlayers.py:824-833 where the norm is not folded. */
 /* The producer of those images: ds_inorm_silu (GroupNorm(C,C) / GroupRMSNorm(C,C) + SiLU, commonlayers.py:766-770, 372-384, 824,
- * 829) with the result written pre-split instead of as fp32 -- the same 8 bytes per element, values bit-identical to ds_inorm_silu's for planes of up to 1024 floats (beyond that the statistics are summed in
- * another order).  Planes of H*W <= 4096 floats, H*W a multiple of 4: ds_inorm_silu_images_supported. */
+ * 829) with the result written pre-split instead of as fp32 -- the same 8 bytes per element, values bit-identical to ds_inorm_silu's (which
+ * reduces every plane this form takes one wave per plane, in the same order).  Planes of H*W <= 4096 floats, H*W a multiple of 4: ds_inorm_silu_images_supported. */
 int ds_inorm_silu_images_supported(int H, int W);
 int ds_inorm_silu_images(void* images, const float* x, const float* w, const float* b, int B, int C, int H, int W, float eps,
                          int kind, void* stream);

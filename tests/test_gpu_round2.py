@@ -603,19 +603,10 @@ def test_norm_images_and_image_input_convolution(dev, shape):
     torch.manual_seed(sum(shape))
     x = torch.randn(B, C, H, W, device=dev) * 1.3 + 0.2
     w, b = torch.randn(C, device=dev), torch.randn(C, device=dev)
-    exact = H * W <= 1024                   # larger planes: the statistics are summed in another order than ds_inorm_silu's
-    for kind in (0, 1):
+    for kind in (0, 1):                     # every plane the image form takes: ds_inorm_silu sums it in the same order
         act = ops.inorm_silu(x, w, b, kind=kind)
         img = ops.inorm_silu_images(x, w, b, kind)
-        if exact:
-            assert torch.equal(img.view(torch.int32), _torch_images(act).view(torch.int32))
-        else:
-            nch = (C + 15) // 16
-            v = img.view(torch.float16).view(B, nch, 2, 2, H + 2, W + 2, 8).float()
-            dec = (v[:, :, 0] + v[:, :, 1]).permute(0, 1, 2, 5, 3, 4).reshape(B, nch * 16, H + 2, W + 2)
-            assert float(dec[:, :, 0].abs().max()) == 0.0 and float(dec[:, :, :, -1].abs().max()) == 0.0
-            assert float(dec[:, C:].abs().max()) == 0.0 if nch * 16 > C else True
-            assert float((dec[:, :C, 1:-1, 1:-1] - act).norm() / act.norm()) < 1e-6
+        assert torch.equal(img.view(torch.int32), _torch_images(act).view(torch.int32))
     even = ((C + 15) // 16) % 2 == 0
     wt = torch.randn(C, C, 3, 3, device=dev) / (3 * C ** 0.5)
     pw = ops.pack_conv(wt, "fp16x3")
@@ -629,10 +620,7 @@ def test_norm_images_and_image_input_convolution(dev, shape):
     ts_b = torch.zeros_like(ts_a)
     want = ops.conv(act, pw, bias=bias, shift=shift, res1=res, tile_stats=ts_a, in_amax=ops.NORMALISED)   # as the networks call it
     got = ops.conv_img(img, pw, B, C, H, W, bias=bias, shift=shift, res1=res, tile_stats=ts_b)
-    if exact:
-        assert torch.equal(got, want) and torch.equal(ts_a, ts_b)
-    else:
-        assert float((got - want).norm() / want.norm()) < 2e-6
+    assert torch.equal(got, want) and torch.equal(ts_a, ts_b)
 
 
 def test_network_with_norm_images_is_bit_identical(M, dev):

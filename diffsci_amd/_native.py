@@ -156,6 +156,7 @@ _PROTOS = {
     # (the flags word closes these two lists, as ds_conv2d_h3_pc's)
     "ds_box_scatter3d": (c_int, [_P, _P, c_int, c_int, c_int, c_int, c_longlong, c_longlong, c_longlong, c_int, c_int, c_int,
                                  c_int, c_int, c_int, c_int, c_int, c_int, _P, c_int]),
+    "ds_crop_blend": (c_int, [_P, _P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, _P, _P, _P, _P, c_int]),
     "ds_si_inpaint_counters": (c_uint64, [c_int, c_size_t, c_int]),
     "ds_si_inpaint_step": (c_int, [_P, _P, _P, _P, _P, POINTER(EvalCoef), POINTER(SIStep), _P, _P, _P, _P, _P, _P, _P, c_uint64,
                                    c_int, c_size_t, _P, c_int]),

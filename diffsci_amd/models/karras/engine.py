@@ -116,7 +116,10 @@ def model_signature(model):
     for d, name in slots[2]:
         p = d[name]
         out.append((p.data_ptr(), tensor_version(p)) if p is not None else None)
-    return tuple(out), tuple(getattr(model, a, None) for a in MODEL_SWITCHES)
+    sig = tuple(out), tuple(getattr(model, a, None) for a in MODEL_SWITCHES)
+    # a wrapper around a network (extra.DiffusionPeriodizer: pad, blend_width, dimension) adds what a capture bakes in of itself
+    own = getattr(model, "plan_signature", None)
+    return sig if own is None else sig + (own(),)
 
 
 class ModuleSource:

@@ -1398,6 +1398,131 @@ def box_scatter3d(src, src_start, dst, dst_start, size):
     return dst
 
 
+# ---------------------------------------------------------------- DiffusionPeriodizer's two sides (extra/periodizer.py)
+def _per_axis(v, n, what, who):
+    """pad / blend_width: an int, or one int per spatial axis -> a tuple of n ints."""
+    if isinstance(v, bool) or (not isinstance(v, int) and not isinstance(v, (tuple, list, torch.Size))):
+        raise TypeError(f"{who}: {what} must be an int or {n} ints; got {v!r}")
+    if isinstance(v, int):
+        return (v,) * n
+    if len(v) != n or any(isinstance(a, bool) or not isinstance(a, int) for a in v):
+        raise ValueError(f"{who}: {what} must be an int or {n} ints; got {v!r}")
+    return tuple(int(a) for a in v)
+
+
+def _spatial(t, what, who):
+    """A [B, C, *S] tensor of 2 or 3 spatial axes -> (planes, box axes): a field's box is (1, H, W) over B*C planes."""
+    if not isinstance(t, torch.Tensor):
+        raise TypeError(f"{who}: {what} must be a torch.Tensor")
+    if t.dtype != torch.float32:
+        raise TypeError(f"{who}: {what} has dtype {t.dtype}; the HIP path is fp32 only")
+    if t.dim() not in (4, 5):
+        raise ValueError(f"{who}: {what} must be [B, C, H, W] or [B, C, D, H, W]; got {tuple(t.shape)}")
+    S = tuple(t.shape[2:])
+    if min(S) < 1:
+        raise ValueError(f"{who}: {what} has an empty spatial axis {S}")
+    if max(S) >= 1 << 31 or t.shape[0] * t.shape[1] >= 1 << 31:
+        raise ValueError(f"{who}: {what} has axes beyond 31 bits {tuple(t.shape)}")
+    return t.shape[0] * t.shape[1], S
+
+
+def periodic_expand(x, pad, out=None):
+    """x [B, C, *S] (2 or 3 spatial axes) -> [B, C, *(S + 2 pad)]: x tiled periodically by `pad` cells per side (an int or one per
+    axis; longer than the axis spans several periods) -- DiffusionPeriodizer.expand_periodic (periodizer.py:76-101), whose
+    periodic_getitem_extended on slice(-p, size + p) is ds_box_copy3d's wrap.  One launch; a field's box is (1, H, W) over B*C
+    planes.  out: the result buffer (not sharing bytes with x)."""
+    who = "periodic_expand"
+    planes, S = _spatial(x, "x", who)
+    p = _per_axis(pad, len(S), "pad", who)
+    if min(p) < 0:
+        raise ValueError(f"{who}: negative pad {p}")
+    E = tuple(s + 2 * a for s, a in zip(S, p))
+    if max(E) >= 1 << 31:
+        raise ValueError(f"{who}: expanded axes beyond 31 bits {E}")
+    if out is not None and not isinstance(out, torch.Tensor):
+        raise TypeError(f"{who}: out must be a torch.Tensor")
+    out = _out(out, tuple(x.shape[:2]) + E, x)
+    if _overlap(x, out):
+        raise ValueError(f"{who}: x and out share storage")
+    px, po = _p(x, "x"), _p(out, "out")
+    if planes == 0:
+        return out
+    S3, E3, p3 = (1,) * (3 - len(S)) + S, (1,) * (3 - len(S)) + E, (0,) * (3 - len(S)) + p
+    if E3[0] * E3[1] >= (1 << 31) - (1 << 20):
+        raise ValueError(f"{who}: axes beyond 31 bits {E}")
+    N.check(N.lib().ds_box_copy3d(po, px, planes, S3[0], S3[1], S3[2], -p3[0], -p3[1], -p3[2], E3[0], E3[1], E3[2], 0, 0, 0,
+                                  E3[0], E3[1], E3[2], _stream()), "ds_box_copy3d")
+    return out
+
+
+_BLEND_WEIGHTS = {}
+
+
+def blend_weights(blend_width, device):
+    """The cosine tables of cosine_blend_boundaries (periodizer.py:160-161), one fp32 tensor of bw floats on `device` per axis
+    (None for a width <= 0): the reference's torch expression evaluated in fp32 on the CPU, so the kernel multiplies by the
+    reference's own weights.  blend_width: an int or a tuple of ints.  Cached per (width, device)."""
+    widths = (blend_width,) if isinstance(blend_width, int) and not isinstance(blend_width, bool) else tuple(blend_width)
+    device = torch.device(device)
+    out = []
+    for bw in widths:
+        if isinstance(bw, bool) or not isinstance(bw, int):
+            raise TypeError(f"blend_weights: blend_width must be ints; got {blend_width!r}")
+        if bw <= 0:
+            out.append(None)
+            continue
+        w = _BLEND_WEIGHTS.get((bw, str(device)))
+        if w is None:
+            with torch.inference_mode(False):
+                positions = torch.arange(bw, dtype=torch.float32)
+                w = (0.5 * (1 - torch.cos(torch.pi * (positions + 0.5) / bw))).to(device)
+            _BLEND_WEIGHTS[(bw, str(device))] = w
+        out.append(w)
+    return tuple(out)
+
+
+def crop_blend(y, pad, blend_width, out=None, weights=None):
+    """y [B, C, *(S + 2 pad)] -> [B, C, *S]: crop_center then cosine_blend_boundaries (periodizer.py:103-199) in one launch
+    (ds_crop_blend: the axes in tensor order, an axis with width <= 0 or 2 width >= size skipped, bit-equal to the reference's
+    fp32 arithmetic on the same weights).  pad, blend_width: an int or one per spatial axis.  weights: the per-axis tables
+    (default: blend_weights(blend_width, y.device)); out: the result buffer (not sharing bytes with y)."""
+    who = "crop_blend"
+    planes, E = _spatial(y, "y", who)
+    nd = len(E)
+    p, bw = _per_axis(pad, nd, "pad", who), _per_axis(blend_width, nd, "blend_width", who)
+    if min(p) < 0 or min(bw) < 0:
+        raise ValueError(f"{who}: negative pad {p} or blend_width {bw}")
+    S = tuple(e - 2 * a for e, a in zip(E, p))
+    if min(S) < 1:
+        raise ValueError(f"{who}: pad {p} leaves nothing of y's spatial axes {E}")
+    if weights is None:
+        weights = blend_weights(bw, y.device)
+    if not isinstance(weights, (tuple, list)) or len(weights) != nd:
+        raise ValueError(f"{who}: weights must be one table (or None) per spatial axis")
+    for w, b, s in zip(weights, bw, S):
+        if w is None:
+            if b > 0 and 2 * b < s:
+                raise ValueError(f"{who}: no weight table for an axis that is blended (width {b} of {s})")
+        elif not isinstance(w, torch.Tensor) or w.dim() != 1 or w.numel() < b:
+            raise ValueError(f"{who}: a weight table must be a 1-D tensor of at least blend_width floats")
+    if out is not None and not isinstance(out, torch.Tensor):
+        raise TypeError(f"{who}: out must be a torch.Tensor")
+    out = _out(out, tuple(y.shape[:2]) + S, y)
+    if _overlap(y, out):
+        raise ValueError(f"{who}: y and out share storage")
+    if (S[0] * S[1] if nd == 3 else S[0]) >= (1 << 31) - (1 << 20):            # the launch's rows per plane
+        raise ValueError(f"{who}: axes beyond 31 bits {S}")
+    py, po = _p(y, "y"), _p(out, "out")
+    pw = [_p(w, "weights") for w in weights]
+    if planes == 0:
+        return out
+    lead = 3 - nd
+    S3, p3, b3, w3 = (1,) * lead + S, (0,) * lead + p, (0,) * lead + bw, [None] * lead + pw
+    N.check(N.lib().ds_crop_blend(po, py, planes, S3[0], S3[1], S3[2], p3[0], p3[1], p3[2], b3[0], b3[1], b3[2], w3[0], w3[1],
+                                  w3[2], _stream(), 0), "ds_crop_blend")
+    return out
+
+
 def conv_tile_count(H, W):
     """Pixel tiles per channel plane in the fp16x3 kernels' tile_stats layout."""
     return N.lib().ds_conv_tile_count(int(H), int(W))

@@ -694,6 +694,22 @@ int ds_box_copy3d(float* dst, const float* src, int planes, int S0, int S1, int 
 int ds_box_scatter3d(float* dst, const float* src, int planes, int D0, int D1, int D2, long long d0, long long d1, long long d2,
                      int S0, int S1, int S2, int s0, int s1, int s2, int L0, int L1, int L2, void* stream, int flags);
 
+/* The output side of DiffusionPeriodizer (extra/periodizer.py:103-199) in one pass, fp32: crop_center, then
+ * cosine_blend_boundaries, of the network's output on the periodically expanded state,
+ *   y [planes, A0+2p0, A1+2p1, A2+2p2] -> out [planes, A0, A1, A2], both dense (a field [B,C,H,W]: A0 = 1, p0 = 0, bw0 = 0).
+ * The crop takes y[n, p0+i, p1+j, p2+k].  The axes are then blended in tensor order, a later axis blending the values the earlier
+ * one blended (a corner reads 8 elements of y, an edge 4, a face 2, the interior 1).  Axis a is active iff bw_a > 0 and
+ * 2 bw_a < A_a; an inactive axis is the identity.  On an active axis, for position q with m = min(q, A-1-q):
+ *   m < bw:   v'(q) = fl( fl(w[m] * v(q)) + fl( fl(1 - w[m]) * v(A-1-q) ) )      else v'(q) = v(q)
+ * with both strips read from the axis' pre-blend values.  Products and sum are rounded separately (no FMA), so with
+ * w_a[i] = 0.5 (1 - cos(pi (i + 0.5) / bw_a)) evaluated in fp32 by the caller the result equals the reference's fp32 result bit
+ * for bit.  w0, w1, w2: device tables of bw_a floats (NULL allowed on an inactive axis only); nothing transcendental runs on the
+ * device.  Every output element is written once; no cropped intermediate exists.  DS_ERR_SHAPE before any launch: non-positive
+ * extents, a negative pad or width, an active axis without its table, out and y overlapping; DS_ERR_UNSUPPORTED: flags != 0
+ * (none defined; the word closes the list).  Element offsets are 64-bit; A0 * A1 < 2^31. */
+int ds_crop_blend(float* out, const float* y, int planes, int A0, int A1, int A2, int p0, int p1, int p2, int bw0, int bw1, int bw2,
+                  const float* w0, const float* w1, const float* w2, void* stream, int flags);
+
 /* ------------------------------------------------------------------------------------
  * The Euler-Maruyama inpainting step of the stochastic-interpolant sampler (flowfield.py:546-641, 783-793): everything one inner
  * iteration of SIModule.inpaint does after the network call, in one pass.  x, f, fu, x_out [B, n]; x_orig, mask [n], shared by

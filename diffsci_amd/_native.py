@@ -119,6 +119,7 @@ _PROTOS = {
     "ds_attention_h3": (c_int, [_P, _P, c_int, c_int, c_int, _P, _P, _P]),
     "ds_attention_h3_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
     "ds_attention_h3_ws": (c_int, [_P, _P, _P, c_int, c_int, c_int, _P, _P, _P]),
+    "ds_attention_h3_xkv": (c_int, [_P, _P, _P, _P, c_int, c_int, c_int, _P, _P, _P, _P, _P, c_int]),    # the flags word closes the list
     "ds_attention_h3_heads_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int]),
     "ds_attention_h3_heads": (c_int, [_P, _P, _P, c_int, c_int, c_int, c_int, _P, _P, _P]),
     "ds_attention_heads_generic": (c_int, [_P, _P, c_int, c_int, c_int, c_int, _P]),

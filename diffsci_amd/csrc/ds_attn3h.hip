@@ -6,6 +6,8 @@
 // stay in fp32 on the accumulators.  Domain: |q|, |k|, |v| < 65504 and not far below 1 -- or, with in_amax [2][B] (the
 // per-sample max |q, k| and max |v| the in-projection left, ds_conv_epilogue.h), any magnitude: q and k are staged times
 // 2^kqk, v times 2^kv, S is read back times 2^-2kqk inside the softmax's FMA and O times 2^-kv with the final 1 / l.
+// The kernels carry one exponent row each for q, k and v (q times 2^aq, k times 2^ak, S times 2^-(aq+ak)); the qkv entry
+// points hand their one q-and-k row to both, ds_attention_h3_xkv hands three.
 //
 // Layout: operands arrive channel-major ([B, 3E, L], what the 1x1 projections write) and the
 // output is channel-major ([B, E, L]).  The regrouping the MFMA wants happens while staging:
@@ -61,9 +63,10 @@ __device__ __forceinline__ f16x8 as_f16x8(u32x4 v) { return __builtin_bit_cast(f
 // rows [h d, (h+1) d) of each third of qkv [B, 3 heads d, L] and writes rows [h d, (h+1) d) of out [B, heads d, L].
 // MH = false is the single-head kernel exactly (heads = 1, nb = gridDim.y: the compiler sees the same code).
 template <int ET, bool IMG, bool MH>
-__global__ __launch_bounds__(NT) void k_attn3h(float* out, const float* __restrict__ qkv, const u32x4* __restrict__ kimg,
-                                               const u32x4* __restrict__ vimg, int L, int heads, int nb, float scale, float thr,
-                                               const unsigned* in_amax, unsigned* out_amax) {
+__global__ __launch_bounds__(NT) void k_attn3h(float* out, const float* __restrict__ q, size_t q_bs,
+                                               const u32x4* __restrict__ kimg, const u32x4* __restrict__ vimg, int L, int heads,
+                                               float scale, float thr, const unsigned* q_amax, const unsigned* k_amax,
+                                               const unsigned* v_amax, unsigned* out_amax) {
   constexpr int E = 32 * ET;                         // the head width
   constexpr int NDG = E / 8;                         // d-groups of 8
   constexpr int NS = E / 16;                         // k-slabs of the S^T product
@@ -95,20 +98,24 @@ __global__ __launch_bounds__(NT) void k_attn3h(float* out, const float* __restri
   const int row = (int)b_u;
   const int b = MH ? row / heads : row, h = MH ? row - b * heads : 0;
   const int Etot = MH ? E * heads : E;               // channels of one third of qkv
-  const int B = MH ? nb : (int)gridDim.y;
   const int q0_raw = ((int)qblk * 4 + wv) * 32;
   const bool active = q0_raw < L;                    // a wave past the last query block recomputes
   const int q0 = active ? q0_raw : L - 32;           // the last block and does not store (no branches
                                                      // around the MFMA pipeline: they cost registers)
-  const float* Qt = qkv + ((size_t)b * 3 * Etot + (size_t)h * E) * L;
+  // q: the queries [.., E tot, L] with batch stride q_bs.  IMG reads nothing else from it; the form that stages in the workgroup
+  // reads K and V behind Q, i.e. q is qkv [B, 3 Etot, L]
+  const float* Qt = q + (size_t)b * q_bs + (size_t)h * E * L;
   const float* Kt = Qt + (size_t)Etot * L;
   const float* Vt = Kt + (size_t)Etot * L;
-  // the sample's activation exponents (0 without in_amax): q, k times 2^ak, v times 2^av; S times 2^-2ak, O times 2^-av -- all exact
-  const int ak = ds_epi::act_exponent_of(ds_epi::act_bits(in_amax, b), -60, 60);
-  const int av = ds_epi::act_exponent_of(ds_epi::act_bits(in_amax, B + b), -120, 120);
+  // the sample's activation exponents (0 without a row): q times 2^aq, k times 2^ak, v times 2^av; S times 2^-(aq+ak), O times
+  // 2^-av -- all exact
+  const unsigned q_bits = ds_epi::act_bits(q_amax, b), k_bits = ds_epi::act_bits(k_amax, b), v_bits = ds_epi::act_bits(v_amax, b);
+  const int aq = ds_epi::act_exponent_of(q_bits, -60, 60);           // the three loads are in flight together: one round trip
+  const int ak = ds_epi::act_exponent_of(k_bits, -60, 60);
+  const int av = ds_epi::act_exponent_of(v_bits, -120, 120);
   const float a_in = ds_epi::pow2f(ak), v_in = ds_epi::pow2f(av);
-  const float s_un = ds_epi::pow2f(-2 * ak), o_un = ds_epi::pow2f(-av);
-  scale = ds_epi::mul_pow2(scale, ak);
+  const float s_un = ds_epi::pow2f(-(aq + ak)), o_un = ds_epi::pow2f(-av);
+  scale = ds_epi::mul_pow2(scale, aq);
 
   // ---- Q fragments: lane (query li, half lh) holds d = 16s + 8lh + 0..7, scaled, split ----
   u32x4 qh[NS], ql[NS];
@@ -459,21 +466,21 @@ __global__ __launch_bounds__(NT) void k_attn3h(float* out, const float* __restri
 // Pre-pass of the IMG form: one workgroup per (key tile, sample) writes the tile's K and V images
 //   K [piece][d-group][key 32][8 d]   V [piece][key-group][d][8 keys]        (the LDS layouts above)
 // with the split every attention workgroup would otherwise redo.  Reads K, V once (8 B/elt), writes as many bytes.
+// ksrc / vsrc: the keys and the values [.., E tot, L] with batch strides k_bs / v_bs -- two thirds of qkv, or (ds_attention_h3_xkv)
+// one tensor x for both, whose second walk over the same 32-key tile mostly hits cache.
 // MH: one workgroup per (key tile, sample, head), images ordered by the (sample, head) row as the attention kernel reads them.
 template <int ET, bool MH>
 __global__ __launch_bounds__(NT) void k_attn_images(u32x4* __restrict__ kimg, u32x4* __restrict__ vimg,
-                                                   const float* __restrict__ qkv, int L, int heads, int nb,
-                                                   const unsigned* in_amax) {
+                                                   const float* __restrict__ ksrc, size_t k_bs, const float* __restrict__ vsrc,
+                                                   size_t v_bs, int L, int heads, const unsigned* k_amax, const unsigned* v_amax) {
   constexpr int E = 32 * ET, NDG = E / 8;
   constexpr int KITEMS = NDG * KB, VITEMS = E * 4;
   const int tid = threadIdx.x, kb = blockIdx.x, row = blockIdx.y, nkb = L / KB;
   const int b = MH ? row / heads : row, h = MH ? row - b * heads : 0;
-  const int Etot = MH ? E * heads : E;
-  const int B = MH ? nb : (int)gridDim.y;
-  const float a_in = ds_epi::pow2f(ds_epi::act_exponent_of(ds_epi::act_bits(in_amax, b), -60, 60));       // the attention kernel's exponents
-  const float v_in = ds_epi::pow2f(ds_epi::act_exponent_of(ds_epi::act_bits(in_amax, B + b), -120, 120));
-  const float* Kt = qkv + (((size_t)b * 3 + 1) * Etot + (size_t)h * E) * L + (size_t)kb * KB;
-  const float* Vt = Kt + (size_t)Etot * L;
+  const float a_in = ds_epi::pow2f(ds_epi::act_exponent_of(ds_epi::act_bits(k_amax, b), -60, 60));        // the attention kernel's exponents
+  const float v_in = ds_epi::pow2f(ds_epi::act_exponent_of(ds_epi::act_bits(v_amax, b), -120, 120));
+  const float* Kt = ksrc + (size_t)b * k_bs + (size_t)h * E * L + (size_t)kb * KB;
+  const float* Vt = vsrc + (size_t)b * v_bs + (size_t)h * E * L + (size_t)kb * KB;
   u32x4* Kd = kimg + ((size_t)row * nkb + kb) * (2 * KITEMS);
   u32x4* Vd = vimg + ((size_t)row * nkb + kb) * (2 * VITEMS);
   for (int e = tid; e < KITEMS; e += NT) {
@@ -503,9 +510,22 @@ __global__ __launch_bounds__(NT) void k_attn_images(u32x4* __restrict__ kimg, u3
   }
 }
 
+// What the two kernels read: queries, keys and values [B, heads * E, L] by base and batch stride (in floats), and the exponent row
+// [B] of each (NULL: none).
+struct AttnSrc {
+  const float *q, *k, *v;
+  size_t q_bs, k_bs, v_bs;
+  const unsigned *q_amax, *k_amax, *v_amax;
+};
+// qkv [B, 3 Etot, L] with in_amax [2][B]: one row for q and k, one for v
+AttnSrc qkv_src(const float* qkv, int B, int Etot, int L, const unsigned* in_amax) {
+  const size_t third = (size_t)Etot * L;
+  return AttnSrc{qkv, qkv + third, qkv + 2 * third, 3 * third, 3 * third, 3 * third, in_amax, in_amax, in_amax ? in_amax + B : nullptr};
+}
+
 template <int ET, bool IMG, bool MH>
-int launch_attn3h(float* out, const float* qkv, void* workspace, int B, int heads, int L, float scale, const unsigned* in_amax,
-                  unsigned* out_amax, hipStream_t s) {
+int launch_attn3h(float* out, const AttnSrc& a, void* workspace, int B, int heads, int L, float scale, unsigned* out_amax,
+                  hipStream_t s) {
   constexpr int E = 32 * ET;                                              // the head width
   const size_t lds = (size_t)2 * (2 * (E / 8) * KB + 2 * 4 * E) * 16;    // K and V, double-buffered
   if (lds > 48 * 1024) {
@@ -518,14 +538,30 @@ int launch_attn3h(float* out, const float* qkv, void* workspace, int B, int head
   if (IMG) {
     kimg = reinterpret_cast<u32x4*>(workspace);
     vimg = kimg + (size_t)rows * L * (E / 4);                             // K images: rows * (L/32) tiles * 8E vectors
-    hipLaunchKernelGGL((k_attn_images<ET, MH>), dim3(L / KB, rows), dim3(NT), 0, s, kimg, vimg, qkv, L, heads, B, in_amax);
+    hipLaunchKernelGGL((k_attn_images<ET, MH>), dim3(L / KB, rows), dim3(NT), 0, s, kimg, vimg, a.k, a.k_bs, a.v, a.v_bs, L, heads,
+                       a.k_amax, a.v_amax);
     DS_CHECK_LAUNCH("ds_attention_h3 (images)");
   }
   dim3 g((L + 127) / 128, rows);
-  hipLaunchKernelGGL((k_attn3h<ET, IMG, MH>), g, dim3(NT), lds, s, out, qkv, kimg, vimg, L, heads, B, scale, RESCALE_T, in_amax,
-                     out_amax);
+  hipLaunchKernelGGL((k_attn3h<ET, IMG, MH>), g, dim3(NT), lds, s, out, a.q, a.q_bs, kimg, vimg, L, heads, scale, RESCALE_T,
+                     a.q_amax, a.k_amax, a.v_amax, out_amax);
   DS_CHECK_LAUNCH("ds_attention_h3");
   return DS_OK;
+}
+
+// Single head.  The image form reads a.q, a.k and a.v where they are; the other form reads K and V behind Q (a = qkv_src).
+template <bool IMG>
+int attention_h3_src(float* out, const AttnSrc& a, void* workspace, int B, int E, int L, unsigned* out_amax, hipStream_t s) {
+  const float scale = (float)sqrt(1.0 / (double)E);
+  switch (E) {
+    case 32: return launch_attn3h<1, IMG, false>(out, a, workspace, B, 1, L, scale, out_amax, s);
+    case 64: return launch_attn3h<2, IMG, false>(out, a, workspace, B, 1, L, scale, out_amax, s);
+    case 128: return launch_attn3h<4, IMG, false>(out, a, workspace, B, 1, L, scale, out_amax, s);
+    case 256: return launch_attn3h<8, IMG, false>(out, a, workspace, B, 1, L, scale, out_amax, s);
+    default:
+      ds::set_error("ds_attention_h3: E=%d unsupported (32, 64, 128, 256)", E);
+      return DS_ERR_UNSUPPORTED;
+  }
 }
 
 template <bool IMG>
@@ -539,17 +575,7 @@ int attention_h3(float* out, const float* qkv, void* workspace, int B, int E, in
   DS_REQUIRE(!IMG || (workspace && (reinterpret_cast<uintptr_t>(workspace) & 15u) == 0), DS_ERR_NULL,
              "ds_attention_h3_ws: a 16-byte aligned workspace of ds_attention_h3_workspace_bytes(B, E, L) bytes is required");
   if (B == 0) return DS_OK;
-  const float scale = (float)sqrt(1.0 / (double)E);
-  hipStream_t s = ds::as_stream(stream);
-  switch (E) {
-    case 32: return launch_attn3h<1, IMG, false>(out, qkv, workspace, B, 1, L, scale, in_amax, out_amax, s);
-    case 64: return launch_attn3h<2, IMG, false>(out, qkv, workspace, B, 1, L, scale, in_amax, out_amax, s);
-    case 128: return launch_attn3h<4, IMG, false>(out, qkv, workspace, B, 1, L, scale, in_amax, out_amax, s);
-    case 256: return launch_attn3h<8, IMG, false>(out, qkv, workspace, B, 1, L, scale, in_amax, out_amax, s);
-    default:
-      ds::set_error("ds_attention_h3: E=%d unsupported (32, 64, 128, 256)", E);
-      return DS_ERR_UNSUPPORTED;
-  }
+  return attention_h3_src<IMG>(out, qkv_src(qkv, B, E, L, in_amax), workspace, B, E, L, out_amax, ds::as_stream(stream));
 }
 
 bool mfma_head_width(int d) { return d == 32 || d == 64 || d == 128 || d == 256; }
@@ -629,6 +655,24 @@ extern "C" int ds_attention_h3_ws(float* out, const float* qkv, void* workspace,
   return attention_h3<true>(out, qkv, workspace, B, E, L, in_amax, out_amax, stream);
 }
 
+extern "C" int ds_attention_h3_xkv(float* out, const float* q, const float* x, void* workspace, int B, int E, int L,
+                                   const unsigned* q_amax, const unsigned* k_amax, const unsigned* v_amax, unsigned* out_amax,
+                                   void* stream, int flags) {
+  DS_REQUIRE(out && q && x, DS_ERR_NULL, "ds_attention_h3_xkv: NULL pointer");
+  DS_REQUIRE(flags == 0, DS_ERR_UNSUPPORTED, "ds_attention_h3_xkv: flags=%d must be 0", flags);
+  DS_REQUIRE(B >= 0 && E > 0 && L > 0, DS_ERR_SHAPE, "ds_attention_h3_xkv: bad shape B=%d E=%d L=%d", B, E, L);
+  DS_REQUIRE(L % 32 == 0, DS_ERR_UNSUPPORTED, "ds_attention_h3_xkv: L=%d must be a multiple of 32", L);
+  DS_REQUIRE(B < 65536 && L / 32 < 65536 * 32, DS_ERR_SHAPE, "ds_attention_h3_xkv: B=%d exceeds grid.y", B);
+  DS_REQUIRE(((reinterpret_cast<uintptr_t>(q) | reinterpret_cast<uintptr_t>(x)) & 15u) == 0, DS_ERR_SHAPE,
+             "ds_attention_h3_xkv: q and x must be 16-byte aligned");
+  DS_REQUIRE(workspace && (reinterpret_cast<uintptr_t>(workspace) & 15u) == 0, DS_ERR_NULL,
+             "ds_attention_h3_xkv: a 16-byte aligned workspace of ds_attention_h3_workspace_bytes(B, E, L) bytes is required");
+  if (B == 0) return DS_OK;
+  const size_t bs = (size_t)E * L;
+  return attention_h3_src<true>(out, AttnSrc{q, x, x, bs, bs, bs, q_amax, k_amax, v_amax}, workspace, B, E, L, out_amax,
+                                ds::as_stream(stream));
+}
+
 extern "C" size_t ds_attention_h3_heads_workspace_bytes(int B, int E, int heads, int L) {
   if (B <= 0 || E <= 0 || L <= 0 || heads <= 0 || E % heads || !mfma_head_width(E / heads) || L % 32) return 0;
   return (size_t)B * L * E * 8;                      // the images of every (sample, head) row: as many bytes as one head of E
@@ -659,15 +703,16 @@ extern "C" int ds_attention_h3_heads(float* out, const float* qkv, void* workspa
   DS_REQUIRE(!workspace || (reinterpret_cast<uintptr_t>(workspace) & 15u) == 0, DS_ERR_SHAPE,
              "ds_attention_h3_heads: the workspace must be 16-byte aligned");
   const bool img = workspace != nullptr;
+  const AttnSrc a = qkv_src(qkv, B, E, L, in_amax);
   switch (d) {
-    case 32: return img ? launch_attn3h<1, true, true>(out, qkv, workspace, B, heads, L, scale, in_amax, out_amax, s)
-                        : launch_attn3h<1, false, true>(out, qkv, nullptr, B, heads, L, scale, in_amax, out_amax, s);
-    case 64: return img ? launch_attn3h<2, true, true>(out, qkv, workspace, B, heads, L, scale, in_amax, out_amax, s)
-                        : launch_attn3h<2, false, true>(out, qkv, nullptr, B, heads, L, scale, in_amax, out_amax, s);
-    case 128: return img ? launch_attn3h<4, true, true>(out, qkv, workspace, B, heads, L, scale, in_amax, out_amax, s)
-                         : launch_attn3h<4, false, true>(out, qkv, nullptr, B, heads, L, scale, in_amax, out_amax, s);
-    default: return img ? launch_attn3h<8, true, true>(out, qkv, workspace, B, heads, L, scale, in_amax, out_amax, s)
-                        : launch_attn3h<8, false, true>(out, qkv, nullptr, B, heads, L, scale, in_amax, out_amax, s);
+    case 32: return img ? launch_attn3h<1, true, true>(out, a, workspace, B, heads, L, scale, out_amax, s)
+                        : launch_attn3h<1, false, true>(out, a, nullptr, B, heads, L, scale, out_amax, s);
+    case 64: return img ? launch_attn3h<2, true, true>(out, a, workspace, B, heads, L, scale, out_amax, s)
+                        : launch_attn3h<2, false, true>(out, a, nullptr, B, heads, L, scale, out_amax, s);
+    case 128: return img ? launch_attn3h<4, true, true>(out, a, workspace, B, heads, L, scale, out_amax, s)
+                         : launch_attn3h<4, false, true>(out, a, nullptr, B, heads, L, scale, out_amax, s);
+    default: return img ? launch_attn3h<8, true, true>(out, a, workspace, B, heads, L, scale, out_amax, s)
+                        : launch_attn3h<8, false, true>(out, a, nullptr, B, heads, L, scale, out_amax, s);
   }
 }
 

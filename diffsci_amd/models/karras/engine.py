@@ -85,7 +85,7 @@ def copy_condition(dst, src):
 
 
 MODEL_SWITCHES = ("conv_precision", "fuse_norm", "fuse_max_cot", "direct_out", "upsample_parity", "norm_images", "tile_stats_norms",
-                  "exact_input_layer", "capturable", "pool_route", "circular_axes")
+                  "exact_input_layer", "capturable", "pool_route", "circular_axes", "attn_fold")
 
 
 def _tree_slots(model):

@@ -333,6 +333,10 @@ class PUNetG(commonlayers.PeriodicAxes, torch.nn.Module):
         # Standalone norms hand their convolutions pre-split fp16 images (ops.inorm_silu_images / ops.conv_img) where the layer
         # qualifies (_norm_images_ok); DIFFSCI_NORM_IMAGES=0 keeps the fp32 route (A/B runs)
         self.norm_images = os.environ.get("DIFFSCI_NORM_IMAGES", "1") != "0"
+        # Single-head attention blocks on the image-form route fold their K and V projections into the Q and the output projection
+        # (runtime.attention, folded=: an E -> E in-projection instead of E -> 3E, x itself as keys and values);
+        # DIFFSCI_ATTN_FOLD=0 keeps the three projections (A/B runs)
+        self.attn_fold = os.environ.get("DIFFSCI_ATTN_FOLD", "1") != "0"
         self._packed = None
         self._packed_sig = None
         self._ws = Workspace()
@@ -347,6 +351,7 @@ class PUNetG(commonlayers.PeriodicAxes, torch.nn.Module):
         super().drop_caches()
         self.__dict__.pop("_tb_packed", None)
         self.__dict__.pop("_tb_packed_sig", None)
+        self.__dict__.pop("_attn_folded", None)
         self._ws, self._am, self._window_cache = Workspace(), None, {}
 
     # ------------------------------------------------------------------ builders (punetg.py:122-334: same names and arguments)
@@ -1056,13 +1061,47 @@ class PUNetG(commonlayers.PeriodicAxes, torch.nn.Module):
         own = None
         if am is None and self.conv_precision == "fp16x3":           # called outside forward_with_shifts (the 3-D path sets its own)
             own = am = AmaxArena(ws, x.shape[0], x.device)
-        y = runtime.attention(x, pk[(id(att), "in")], in_bias, pk[(id(att), "out")], out_bias, E=x.shape[1],
-                              heads=getattr(m, "num_heads", 1), precision=self.conv_precision, ws=ws, am=am, in_amax=in_amax,
+        E, heads = x.shape[1], getattr(m, "num_heads", 1)
+        folded = None
+        if self.attn_fold:
+            # the unfolded packings stand in for the folded ones (same kind) to ask whether the route is taken at all
+            probe = runtime.FoldedAttention(pk[(id(att), "in")], None, pk[(id(att), "out")], None)
+            if runtime.attention_folds(probe, E, x.shape[2] * x.shape[3], heads, self.conv_precision, self.cosine_attn):
+                folded = self._folded_attention(att)
+        y = runtime.attention(x, pk[(id(att), "in")], in_bias, pk[(id(att), "out")], out_bias, E=E,
+                              heads=heads, precision=self.conv_precision, ws=ws, am=am, in_amax=in_amax,
                               out_amax=out_amax, res1=x if self.config.attn_residual else None, res2=res2, tile_stats=tile_stats,
-                              cosine=self.cosine_attn)
+                              cosine=self.cosine_attn, folded=folded)
         if own is not None:
             own.release()
         return y
+
+    def _folded_attention(self, att):
+        """runtime.FoldedAttention of one attention block (fp16x3 packings of M = Wk^T Wq and W' = Wo Wv with their biases, formed in
+        fp64 from the weights packed_weights() reads), built on first use of the folded route and kept until a projection weight
+        or bias changes.  Not an entry of packed_weights(): the route is taken by some shapes only."""
+        m = att.mhattn
+        if self.inhouse_attn:
+            tracked = [m.q_proj_matrix, m.k_proj_matrix, m.v_proj_matrix, m.o_proj_matrix]
+        else:
+            tracked = [t for t in (m.in_proj_weight, m.out_proj.weight, m.in_proj_bias, m.out_proj.bias) if t is not None]
+        sig = weights_signature(tracked, self.conv_precision)
+        cache = self.__dict__.setdefault("_attn_folded", {})
+        hit = cache.get(id(att))
+        if hit is not None and hit[0] == sig:
+            return hit[1]
+        with torch.no_grad():
+            if self.inhouse_attn:
+                (w_in, w_out), b_in, b_out = m.projection_weights(), None, None
+            else:
+                w_in, w_out, b_in, b_out = m.in_proj_weight, m.out_proj.weight, m.in_proj_bias, m.out_proj.bias
+            E = m.embed_dim
+            M, c, Wp, bp = runtime.fold_attention_weights(w_in, b_in, w_out, b_out)
+            f32 = lambda t: None if t is None else t.float().contiguous()
+            folded = runtime.FoldedAttention(ops.pack_conv(f32(M).reshape(E, E, 1, 1), "fp16x3"), f32(c),
+                                             ops.pack_conv(f32(Wp).reshape(E, E, 1, 1), "fp16x3"), f32(bp))
+        cache[id(att)] = (sig, folded)
+        return folded
 
 
 def _shift_source(shifts, row, B):

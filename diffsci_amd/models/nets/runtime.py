@@ -146,14 +146,52 @@ def _amax_kw(pack, **kw):
     return kw if pack.kind == "fp16x3" else {}
 
 
+class FoldedAttention:
+    """The projections of a single-head block with K and V folded away: w_q, b_q = the packed M = Wk^T Wq and
+    c = Wk^T bq of the E -> E in-projection whose output q' attends over x itself; w_out, b_out = the packed W' = Wo Wv and
+    b' = Wo bv + bo of the out-projection.  Biases may be None (a block without biases)."""
+    __slots__ = ("w_q", "b_q", "w_out", "b_out")
+
+    def __init__(self, w_q, b_q, w_out, b_out):
+        self.w_q, self.b_q, self.w_out, self.b_out = w_q, b_q, w_out, b_out
+
+
+def fold_attention_weights(w_in, b_in, w_out, b_out):
+    """(M, c, W', b') in fp64 from the in-projection [3E, E] (rows q, k, v; bias [3E] or None) and the out-projection [E, E]
+    (bias [E] or None) of a single-head block:
+        scores  (Wq x_i + bq).(Wk x_j + bk) = (Wk^T Wq x_i + Wk^T bq).x_j + a term without j, which the softmax over j removes
+        values  Wo (sum_j p_ij (Wv x_j + bv)) + bo = (Wo Wv)(sum_j p_ij x_j) + (Wo bv + bo), the p_ij summing to 1."""
+    E = w_out.shape[0]
+    w_in, w_out = w_in.detach().double().reshape(3 * E, E), w_out.detach().double().reshape(E, E)
+    wq, wk, wv = w_in[:E], w_in[E:2 * E], w_in[2 * E:]
+    M, Wp = wk.t() @ wq, w_out @ wv
+    c = bp = None
+    if b_in is not None:
+        b_in = b_in.detach().double()
+        c, bp = wk.t() @ b_in[:E], w_out @ b_in[2 * E:]
+    if b_out is not None:
+        bp = b_out.detach().double() + (0 if bp is None else bp)
+    return M, c, Wp, bp
+
+
+def attention_folds(folded, E, L, heads, precision, cosine):
+    """Whether attention() takes the folded route: a bundle of fp16x3 packings, one head, plain (not cosine) logits, and the
+    image form of the attention core -- the only one with a pre-pass for x to feed."""
+    return (folded is not None and folded.w_q.kind == "fp16x3" and folded.w_out.kind == "fp16x3" and heads == 1 and not cosine
+            and ops._attention_uses_images(E, L, precision))
+
+
 def attention(x4, w_in, b_in, w_out, b_out, *, E, heads, precision, ws=None, am=None, in_amax=None, out_amax=None,
-              res1=None, res2=None, tile_stats=None, cosine=False, attn_out=None):
+              res1=None, res2=None, tile_stats=None, cosine=False, attn_out=None, folded=None):
     """Self-attention over the positions of x4 [B, E, H, W], channel-major throughout: in-projection (w_in, b_in: the packed
     [3E, E] 1x1 convolution), the attention core with `heads` heads, out-projection (w_out, b_out) + res1 + res2, leaving
     tile_stats / out_amax of the result where asked.  The three launches read raw tensors: x4 (in_amax: its producer's row;
     None: reduced into a row of `am`, or by the convolution itself), qkv and the attention output, whose exponents travel from
     epilogue to loader through rows of the arena `am` (None: fresh slots).  Buffers come from the pool `ws` (None: torch's
-    allocator); attn_out: a [B, E, L] buffer of the caller's for the attention output.  cosine: unit queries and keys."""
+    allocator); attn_out: a [B, E, L] buffer of the caller's for the attention output.  cosine: unit queries and keys.
+    folded: a FoldedAttention of the same block; where attention_folds() holds, the in-projection is its E -> E one, x4 itself
+    serves as keys and values under its own exponent row, and the out-projection is the folded one -- same result up to
+    rounding, a third of the in-projection's work.  Every other case launches what it launches without the bundle."""
     B, _, Hh, Ww = x4.shape
     L = Hh * Ww
     dev = x4.device
@@ -165,6 +203,20 @@ def attention(x4, w_in, b_in, w_out, b_out, *, E, heads, precision, ws=None, am=
         if ws is not None and t is not None:
             ws.give(t)
 
+    if attention_folds(folded, E, L, heads, precision, cosine):
+        a_q, a_o = (ops.amax_new(B, dev), ops.amax_new(B, dev)) if am is None else (am.row(), am.row())
+        if in_amax is None:                                           # x4's own row: the in-projection's, the keys' and the values'
+            in_amax = ops.absmax_rows(x4, B) if am is None else am.of(x4)
+        q = ops.conv(x4, folded.w_q, bias=folded.b_q, out=take((B, E, Hh, Ww)), in_amax=in_amax, out_amax=a_q)
+        aws = take((ops.attention_workspace_floats(B, E, L, precision),))
+        o = ops.attention_xkv(q.view(B, E, L), x4.view(B, E, L), E, out=take((B, E, L)) if attn_out is None else attn_out,
+                              workspace=aws, q_amax=a_q, x_amax=in_amax, out_amax=a_o)
+        give(aws)
+        y = ops.conv(o.view(B, E, Hh, Ww), folded.w_out, bias=folded.b_out, res1=res1, res2=res2, tile_stats=tile_stats,
+                     out=take(x4.shape), in_amax=a_o, out_amax=out_amax)
+        give(q)
+        give(None if attn_out is not None else o)
+        return y
     a_qkv = a_o = None
     if w_in.kind == "fp16x3":
         a_qkv, a_o = (ops.amax_new(2 * B, dev), ops.amax_new(B, dev)) if am is None else (am.rows(2), am.row())

@@ -1853,6 +1853,37 @@ def attention(qkv, E, out=None, precision="fp32", workspace=None, in_amax=None, 
     return out
 
 
+def attention_xkv(q, x, E, out=None, workspace=None, q_amax=None, x_amax=None, out_amax=None):
+    """Single-head fp16x3 attention in the image form with x as keys AND values (the folded block):
+    q [B, E, L], x [B, E, L] channel-major -> out [B, E, L].  Only where the image form runs (_attention_uses_images(E, L,
+    "fp16x3")): anything else is refused, not rerouted.  workspace: attention_workspace_floats(B, E, L) floats, allocated here
+    when not given.  q_amax, x_amax: int32 [B] each, the exponent rows of q and of x (x's serves the keys and the values);
+    None = reduced here, NORMALISED = no scaling.  out_amax [B]: as attention()."""
+    B, Eq, L = q.shape
+    if Eq != E or tuple(x.shape) != (B, E, L):
+        raise ValueError(f"attention_xkv: q and x must be [B, E={E}, L]; got {tuple(q.shape)} and {tuple(x.shape)}")
+    if not _attention_uses_images(E, L, "fp16x3"):
+        raise ValueError(f"attention_xkv: E={E}, L={L} is outside the image form (E in 32, 64, 128, 256; L % 32 == 0; "
+                         f"L >= {ATTN_IMAGES_MIN_L}, or {ATTN_IMAGES_MIN_L_WIDE} at E = 256)")
+    out = _out(out, (B, E, L), q)
+    pq, px = _p(q, "q"), _p(x, "x")
+    if B == 0:
+        return out
+    if (pq | px) & 15:
+        raise ValueError("attention_xkv: q and x must be 16-byte aligned")
+    if q_amax is None:
+        q_amax = absmax_rows(q, B)
+    if x_amax is None:
+        x_amax = absmax_rows(x, B)
+    paq = None if q_amax is NORMALISED else _pi(q_amax, B, "q_amax")
+    pax = None if x_amax is NORMALISED else _pi(x_amax, B, "x_amax")
+    need = N.lib().ds_attention_h3_workspace_bytes(B, E, L)
+    pws = _p(_workspace(workspace, need, q, "attention workspace too small"), "workspace")
+    N.check(N.lib().ds_attention_h3_xkv(_p(out), pq, px, pws, B, E, L, paq, pax, pax, _pi(out_amax, B, "out_amax"), _stream(), 0),
+            "ds_attention_h3_xkv")
+    return out
+
+
 def linear(x, w, b=None, act=0, out=None):
     M, K = x.shape
     Nn, K2 = w.shape

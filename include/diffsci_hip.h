@@ -494,6 +494,14 @@ int ds_attention_h3(float* out, const float* qkv, int B, int E, int L, const uns
 size_t ds_attention_h3_workspace_bytes(int B, int E, int L);
 int ds_attention_h3_ws(float* out, const float* qkv, void* workspace, int B, int E, int L, const unsigned* in_amax,
                        unsigned* out_amax, void* stream);
+/* The image form with the queries in a tensor of their own and ONE tensor x [B, E, L] serving as keys and as values: the core
+ * of a single-head block whose K and V projections were folded into the Q and the output projection.
+ * q [B, E, L] (batch stride E L), x [B, E, L], both 16-byte aligned; workspace as ds_attention_h3_ws.  q_amax, k_amax, v_amax:
+ * one exponent row [B] each (per-sample max |q|, max |keys|, max |values| as float bits; NULL: no scaling) -- q is staged
+ * times 2^aq, the keys times 2^ak, the logits read back times 2^-(aq + ak); pass x's row as k_amax and as v_amax.  With
+ * q_amax = k_amax the result equals ds_attention_h3_ws on the concatenation [q, x, x] bit for bit.  flags must be 0. */
+int ds_attention_h3_xkv(float* out, const float* q, const float* x, void* workspace, int B, int E, int L, const unsigned* q_amax,
+                        const unsigned* k_amax, const unsigned* v_amax, unsigned* out_amax, void* stream, int flags);
 /* Multi-head self-attention (nn.MultiheadAttention(E, num_heads = heads) core): E % heads == 0, head width d = E / heads.
  * Same channel-major operands: head h reads rows [h d, (h+1) d) of each third of qkv [B, 3E, L] and writes rows
  * [h d, (h+1) d) of out [B, E, L]; logits scaled by 1 / sqrt(d).  d in {32, 64, 128, 256} and L a multiple of 32: the

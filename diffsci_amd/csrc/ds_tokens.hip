@@ -21,17 +21,29 @@ constexpr int NT = 256;
 // ---- LayerNorm(E) + adaLN modulation ------------------------------------------------------------------------------------------
 // A workgroup owns 32 consecutive tokens of one sample: TX = 32 / VEC lanes along the tokens (VEC = 4: 16-byte loads, L % 4 == 0;
 // VEC = 1 otherwise), TY = 256 / TX groups across the channels, thread (tx, ty) holding rows ty, ty + TY, ... in registers (NR of
-// them: the tensor is read once).  Statistics are shifted by the token's first channel K = x[b, 0, l]: d = x - K is held instead of
-// x, mean - K = sum(d) / E, var = sum((d - (mean - K))^2) / E in a second pass over the registers -- no E[x^2] - mean^2, and the mean
-// is never rounded to the magnitude of x (a token at 1e4 +- 1 keeps its 24 bits of the +- 1).  Partial sums: NR terms in the
-// thread, a butterfly over the TY groups of the wave, the four waves through LDS in a fixed order.
+// them: the tensor is read once).  Statistics are centred in two steps.  The token's first channel K = x[b, 0, l] is a pivot only
+// for a first estimate of the mean, m1 = fl(K + sum(x - K) / E); the registers then hold d = x - m1 instead of x, mean - m1 =
+// sum(d) / E, and var = sum((d - (mean - m1))^2) / E in a last pass over the registers -- no E[x^2] - mean^2, and the deviations are
+// never rounded to the magnitude of x: a token at 1e4 +- 1 keeps its 24 bits of the +- 1 (m1 is within a deviation of the mean, so
+// x - m1 is exact there).  Holding x - K itself would round every channel to ulp(K), which is ruinous when channel 0 is an outlier
+// (a "massive activation" of 1e6 among values of order one); m1 is off by at most the rounding of x - K averaged over E, and
+// x - m1 is rounded at the ulp of the deviation itself, the floor of any fp32 LayerNorm.  Each of the three
+// reductions is a pairwise tree in a fixed order: the thread's NR terms by halves (tree_rows; a running sum of 64 or 128 terms
+// loses what a dominant first term's ulp hides from every later one), a butterfly over the TY groups of the wave, the four waves
+// through LDS -- the result is the same bits from run to run.
+template <int LO, int N, class F>
+__device__ __forceinline__ float tree_rows(const F& term) {       // term(LO) + ... + term(LO + N - 1), N a power of two
+  if constexpr (N == 1) return term(LO);
+  else return tree_rows<LO, N / 2>(term) + tree_rows<LO + N / 2, N / 2>(term);
+}
+
 template <int VEC, int NR>
 __global__ __launch_bounds__(NT) void k_token_ln(float* __restrict__ out, const float* __restrict__ x, const float* __restrict__ w,
                                                  const float* __restrict__ bias, const float* __restrict__ mscale,
                                                  const float* __restrict__ mshift, int mstride, int E, int L, float eps,
                                                  unsigned* __restrict__ out_amax) {
   constexpr int TX = 32 / VEC, TY = NT / TX;
-  __shared__ float red[2][4][32];
+  __shared__ float red[3][4][32];
   const int tx = threadIdx.x % TX, ty = threadIdx.x / TX, wave = threadIdx.x >> 6;
   const int b = blockIdx.y;
   const int l0 = blockIdx.x * 32 + tx * VEC;
@@ -39,7 +51,7 @@ __global__ __launch_bounds__(NT) void k_token_ln(float* __restrict__ out, const 
   const float* xb = x + (size_t)b * E * L + l0;
   float d[NR][VEC], K[VEC], s[VEC];
 #pragma unroll
-  for (int j = 0; j < VEC; ++j) K[j] = 0.f, s[j] = 0.f;
+  for (int j = 0; j < VEC; ++j) K[j] = 0.f;
   if (live) {
     if constexpr (VEC == 4) {
       const f32x4 k4 = *reinterpret_cast<const f32x4*>(xb);
@@ -52,34 +64,33 @@ __global__ __launch_bounds__(NT) void k_token_ln(float* __restrict__ out, const 
   for (int r = 0; r < NR; ++r) {
     const int e = ty + r * TY;
 #pragma unroll
-    for (int j = 0; j < VEC; ++j) d[r][j] = 0.f;
+    for (int j = 0; j < VEC; ++j) d[r][j] = K[j];        // rows past E and dead tokens add x - K = 0
     if (live && e < E) {
       if constexpr (VEC == 4) {
         const f32x4 v = *reinterpret_cast<const f32x4*>(xb + (size_t)e * L);
-        d[r][0] = v.x - K[0], d[r][1] = v.y - K[1], d[r][2] = v.z - K[2], d[r][3] = v.w - K[3];
+        d[r][0] = v.x, d[r][1] = v.y, d[r][2] = v.z, d[r][3] = v.w;
       } else {
-        d[r][0] = xb[(size_t)e * L] - K[0];
+        d[r][0] = xb[(size_t)e * L];
       }
     }
-#pragma unroll
-    for (int j = 0; j < VEC; ++j) s[j] += d[r][j];
   }
   const float inv_e = 1.0f / (float)E;
   float dm[VEC], rstd[VEC];
 #pragma unroll
-  for (int pass = 0; pass < 2; ++pass) {
-    if (pass == 1) {
+  for (int pass = 0; pass < 3; ++pass) {
 #pragma unroll
-      for (int j = 0; j < VEC; ++j) s[j] = 0.f;
+    for (int j = 0; j < VEC; ++j) {
+      if (pass == 0) {
+        s[j] = tree_rows<0, NR>([&](int r) { return d[r][j] - K[j]; });
+      } else if (pass == 1) {                            // dm holds m1 here: the registers now hold x - m1, 0 in the rows past E
 #pragma unroll
-      for (int r = 0; r < NR; ++r) {
-        if (ty + r * TY < E) {
-#pragma unroll
-          for (int j = 0; j < VEC; ++j) {
-            const float c = d[r][j] - dm[j];
-            s[j] += c * c;
-          }
-        }
+        for (int r = 0; r < NR; ++r) d[r][j] = ty + r * TY < E ? d[r][j] - dm[j] : 0.f;
+        s[j] = tree_rows<0, NR>([&](int r) { return d[r][j]; });
+      } else {
+        s[j] = tree_rows<0, NR>([&](int r) {
+          const float c = d[r][j] - dm[j];
+          return ty + r * TY < E ? c * c : 0.f;
+        });
       }
     }
 #pragma unroll
@@ -96,7 +107,8 @@ __global__ __launch_bounds__(NT) void k_token_ln(float* __restrict__ out, const 
     for (int j = 0; j < VEC; ++j) {
       const int t = tx * VEC + j;
       const float tot = ((red[pass][0][t] + red[pass][1][t]) + red[pass][2][t]) + red[pass][3][t];
-      if (pass == 0) dm[j] = tot * inv_e;
+      if (pass == 0) dm[j] = K[j] + tot * inv_e;         // m1
+      else if (pass == 1) dm[j] = tot * inv_e;           // mean - m1
       else rstd[j] = 1.0f / sqrtf(tot * inv_e + eps);
     }
   }

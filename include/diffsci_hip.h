@@ -631,8 +631,9 @@ int ds_add(float* out, const float* a, const float* b, size_t n, void* stream);
 
 /* torch.nn.LayerNorm(E) over the embedding axis of every token, then adaln_modulate (difftransformer.py:23-28,148-149,171,174):
  *   out[b,e,l] = ((x[b,e,l] - mean[b,l]) * rstd[b,l] * w[e] + b[e]) * (1 + mod_scale[b*mod_stride + e]) + mod_shift[b*mod_stride + e]
- * mean and the biased variance over e, rstd = 1/sqrt(var + eps).  The statistics are two passes over registers on values shifted
- * by the token's first channel (never E[x^2] - mean^2).  w, b, mod_scale, mod_shift may each be NULL (1, 0, 0, 0).  out_amax
+ * mean and the biased variance over e, rstd = 1/sqrt(var + eps).  The statistics are passes over registers on values centred on
+ * a first estimate of the mean (never E[x^2] - mean^2, no pivot on one sample), every sum a pairwise tree in a fixed order.  w, b,
+ * mod_scale, mod_shift may each be NULL (1, 0, 0, 0).  out_amax
  * (optional, int32 [B], zeroed or merged into): float bits of max |out[b]| for the fp16x3 launch that reads out.  E <= 1024.
  * out may not alias x. */
 int ds_token_layernorm(float* out, const float* x, const float* w, const float* b, const float* mod_scale, const float* mod_shift,

@@ -659,10 +659,10 @@ __global__ __launch_bounds__(512, 2) void k_conv3p(const Conv3hArgs a) {
       f32x4 o[BK];
 #pragma unroll
       for (int k = 0; k < BK; ++k) {
-        const float K = ds_epi::row16_first(v[k].x);
+        const float K = ds_epi::wave_pivot(v[k].x);                      // the median of three of the wave's pixels: every wave is full here
         const f32x4 d = v[k] - K;
         const float sv = ds_epi::row16_sum((d.x + d.y) + (d.z + d.w));
-        const float qv = ds_epi::row16_sum((d.x * d.x + d.y * d.y) + (d.z * d.z + d.w * d.w));
+        const float qv = ds_epi::row16_sum(ds_epi::sumsq4(d));
         o[k] = f32x4{K, sv, qv, 64.f};                                   // the wave's 2 x 32 pixels of the channel
       }
       // row (channel) 4 j + lane / 16 of [64][4] at the tile's head, i.e. inside the region store instructions 0-3 read: this wave's
@@ -685,7 +685,7 @@ __global__ __launch_bounds__(512, 2) void k_conv3p(const Conv3hArgs a) {
     f32x4 pw[4];
 #pragma unroll
     for (int w = 0; w < 4; ++w) pw[w] = *reinterpret_cast<const f32x4*>(&tiles[w * 4096 + 4 * lane]);
-    const float K = pw[0][0];
+    const float K = ds_epi::tile_pivot(pw[0][0], pw[1][0], pw[1][3], pw[2][0], pw[2][3]);
     float S = 0.f, Qs = 0.f, n = 0.f;
 #pragma unroll
     for (int w = 0; w < 4; ++w) {

@@ -33,8 +33,12 @@ struct Args {
   int Cout, H, W;
   // Optional per-(channel, tile) statistics of the stored values, for the normalisation that consumes
   // this tensor: tile_stats[(b*Cout + co)*ntiles + tile] = float4 (K, S, Q, n) with n valid pixels,
-  // K one of the values, S = sum(x - K), Q = sum((x - K)^2).  Shifting by K keeps fp32 sums free of the
-  // mean^2 cancellation; the table kernels (ds_normtab.hip) combine the tiles in fp64.
+  // K any finite shift near the tile's values, S = sum(x - K), Q = sum((x - K)^2).  Shifting by K keeps fp32
+  // sums free of the mean^2 cancellation; the table kernels (ds_normtab.hip) combine the tiles in fp64.
+  // K must be an ORDINARY value of the tile: with an outlier M as the shift every x - K is rounded at ulp(M)
+  // and the waves' recombination adds n (K_w - K)^2 = n M^2 to sums of order n var.  A wave
+  // therefore shifts by the median of three of its pixels (wave_pivot below), a ragged wave by the mean
+  // of its valid pixels, and the tile by the median of its first three waves' shifts (tile_pivot).
   float* tile_stats;
   int tile, ntiles;
   // ds_convup.hip only: the tile is in LOW-resolution coordinates (y0, x0; H, W are the output's) and covers output
@@ -111,9 +115,26 @@ __device__ __forceinline__ float row16_sum(float v) {
   v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x128, 0xF, 0xF, true));  // row_ror:8
   return v;
 }
-// lane 0 of each 16-lane row, broadcast to the row
-__device__ __forceinline__ float row16_first(float v) {
-  return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x150, 0xF, 0xF, true));  // row_share:0
+// lane L of each 16-lane row, broadcast to the row
+template <int L> __device__ __forceinline__ float row16_lane(float v) {
+  return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x150 + L, 0xF, 0xF, true));  // row_share:L
+}
+// The shift of a full wave's statistics of one channel, x = the first element of the lane's four: the median of pixels (0, 0),
+// (0, 20) and (1, 8) of the wave's [2][32] block (lanes 0, 5 and 10 of the channel's 16-lane row) -- three rows in the 16 x 16
+// geometry -- so that neither a single outlier, nor a 2 x 2 block, nor a border column can be the shift.  The element-wise path
+// and the persistent kernel (ds_conv3p.hip) take the same three pixels, ds_convup.hip the like of its [2][64] block.
+__device__ __forceinline__ float wave_pivot(float x) {
+  return __builtin_amdgcn_fmed3f(row16_lane<0>(x), row16_lane<5>(x), row16_lane<10>(x));
+}
+// sum of the squares of a lane's four deviations: one product and three fused multiply-adds.  (The build has -ffp-contract=off;
+// written out, (dx dx + dy dy) + (dz dz + dw dw) is four products and three sums -- the three instructions saved pay for wave_pivot.)
+__device__ __forceinline__ float sumsq4(const f32x4 d) {
+  return __builtin_fmaf(d.x, d.x, __builtin_fmaf(d.y, d.y, __builtin_fmaf(d.z, d.z, d.w * d.w)));
+}
+// The tile's shift from the waves' (K, n): the median of waves 0-2's, wave 0's in place of an absent wave's (wave 0 owns the tile's
+// first rows: present whenever the tile is)
+__device__ __forceinline__ float tile_pivot(float K0, float K1, float n1, float K2, float n2) {
+  return __builtin_amdgcn_fmed3f(K0, n1 > 0.f ? K1 : K0, n2 > 0.f ? K2 : K0);
 }
 
 // W16 = false: the wave's 2 x 32 positions are 2 rows x 32 columns (row = y0 + r, column = x0 + x);
@@ -232,6 +253,8 @@ __device__ __forceinline__ void store_tile_rows(float* tile, const Args& e, cons
     const bool pix_ok = rp.pix_ok;
     const size_t idx_lane = rp.idx_lane, idx_step = rp.idx_step;
     const float cnt_row = stats ? row16_sum(pix_ok ? 4.f : 0.f) : 0.f;     // valid pixels of a channel in this wave: the same for every channel
+    const bool full = e.y0 + (W16 ? 4 : 2) <= e.H && e.x0 + (W16 ? 16 : 32) <= e.W;   // the wave's whole block lies inside the plane
+    const float inv_cnt = cnt_row > 0.f ? 1.f / cnt_row : 0.f;
     const bool want_amax = DS_AMAX_EPILOGUE && e.out_amax != nullptr;
     float amax = 0.f;
     float sK[8 * MT], ssum[8 * MT], ssq[8 * MT], scnt[8 * MT];   // per (half, k): channel 4*(4*half+k) + lane/16, valid in every lane of the row
@@ -304,12 +327,13 @@ __device__ __forceinline__ void store_tile_rows(float* tile, const Args& e, cons
       if (stats) {
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
-          // the row's 16 lanes hold both rows of channel seg>>1 (lanes 0-7: r = 0, 8-15: r = 1); lane 0
-          // is the wave's first pixel of the channel: valid whenever any pixel of the wave is
-          const float K = row16_first(ok[k] ? v[k].x : 0.f);
+          // the row's 16 lanes hold both rows of channel seg>>1 (lanes 0-7: r = 0, 8-15: r = 1)
+          float K;
+          if (full) K = wave_pivot(ok[k] ? v[k].x : 0.f);
+          else K = row16_sum(ok[k] ? (v[k].x + v[k].y) + (v[k].z + v[k].w) : 0.f) * inv_cnt;   // ragged wave: the mean of its valid pixels
           const f32x4 d = v[k] - K;
           const float sv = ok[k] ? (d.x + d.y) + (d.z + d.w) : 0.f;
-          const float qv = ok[k] ? (d.x * d.x + d.y * d.y) + (d.z * d.z + d.w * d.w) : 0.f;
+          const float qv = ok[k] ? sumsq4(d) : 0.f;
           sK[half * 4 + k] = K;
           ssum[half * 4 + k] = row16_sum(sv);
           ssq[half * 4 + k] = row16_sum(qv);
@@ -330,6 +354,10 @@ __device__ __forceinline__ void store_tile_rows(float* tile, const Args& e, cons
   } else {
     // ragged width: element-wise, compact loop (correctness path for odd shapes); one channel per iteration
     float amax = 0.f;
+    // valid pixels of a channel in this wave (lane -> pixel is the same in every iteration)
+    const int lx = lane & 31, ly = e.y0 + (W16 ? 2 * (lane >> 5) + (lx >> 4) : (lane >> 5));
+    const int nvalid = __popcll(__ballot(ly < e.H && e.x0 + (W16 ? (lx & 15) : lx) < e.W));
+    const float inv_cnt = nvalid > 0 ? 1.f / (float)nvalid : 0.f;
     for (int i = lane; i < 32 * MT * 2 * 32; i += 64) {
       const int co = i >> 6, r = (i >> 5) & 1, x = i & 31;
       const int gy = e.y0 + (W16 ? 2 * r + (x >> 4) : r), gxx = e.x0 + (W16 ? (x & 15) : x);
@@ -345,7 +373,12 @@ __device__ __forceinline__ void store_tile_rows(float* tile, const Args& e, cons
         amax = fmaxf(amax, __builtin_fabsf(v));
       }
       if (stats) {
-        const float K = __shfl(v, 0, 64);                              // the wave's first pixel of the channel
+        float K;                                                       // as in the 16-byte path: pixels (0, 0), (0, 20), (1, 8), or the mean
+        if (nvalid == 64) {
+          K = __builtin_amdgcn_fmed3f(__shfl(v, 0, 64), __shfl(v, 20, 64), __shfl(v, 40, 64));
+        } else {
+          K = ds::wave_sum(v) * inv_cnt;                               // v is 0 outside the plane
+        }
         const float d = okv ? v - K : 0.f;
         float sv = d, qv = d * d, nv = okv ? 1.f : 0.f;
 #pragma unroll
@@ -371,7 +404,7 @@ __device__ __forceinline__ void store_tile_stats(const float* tiles, int wave_st
     const int w0 = MT == 1 ? 4 * (t >> 5) : 0, tl = MT == 1 ? (t & 31) : t;
 #pragma unroll
     for (int w = 0; w < 4; ++w) p[w] = *reinterpret_cast<const f32x4*>(&tiles[(w0 + w) * wave_stride + 4 * tl]);
-    const float K = p[0][0];                              // wave 0 owns the tile's first rows: valid if the tile is
+    const float K = tile_pivot(p[0][0], p[1][0], p[1][3], p[2][0], p[2][3]);
     float S = 0.f, Q = 0.f, n = 0.f;
 #pragma unroll
     for (int w = 0; w < 4; ++w) {

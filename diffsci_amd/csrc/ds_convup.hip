@@ -169,11 +169,13 @@ __device__ __forceinline__ void store_half_rows(int m, const float* tile, float*
     if (ok) *reinterpret_cast<f32x4*>(e.out + idx) = v;
     if (e.out_amax) amax = ok ? fmaxf(amax, ds::amax4(v)) : amax;
     if (stats) {
-      // lanes 0-15 / 16-31 of a 32-lane half hold rows r = 0 / 1 of one channel; the shift K is the channel's first value
-      const float K = __shfl(ok ? v.x : 0.f, lane & 32, 64);
+      // lanes 0-15 / 16-31 of a 32-lane half hold rows r = 0 / 1 of one channel; the shift K is the median of pixels (0, 0), (0, 20)
+      // and (0, 40) of the wave's [2][64] block -- (0, 0), (0, 20) and (1, 8) of its [4][32] block in the 16 x 16 geometry:
+      // ds_epi::wave_pivot (which says why) of the half's first 16 lanes, broadcast to the half.  Every wave is full here.
+      const float K = __shfl(ds_epi::wave_pivot(ok ? v.x : 0.f), lane & 32, 64);
       const f32x4 d = v - K;
       float s1 = ok ? (d.x + d.y) + (d.z + d.w) : 0.f;
-      float s2 = ok ? (d.x * d.x + d.y * d.y) + (d.z * d.z + d.w * d.w) : 0.f;
+      float s2 = ok ? ds_epi::sumsq4(d) : 0.f;
       s1 = ds_epi::row16_sum(s1);
       s2 = ds_epi::row16_sum(s2);
       s1 += __shfl_xor(s1, 16, 64);

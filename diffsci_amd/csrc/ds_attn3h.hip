@@ -26,10 +26,22 @@
 // no split VALU work in the loop.  At L = 4096 a tile is otherwise re-split by 32 workgroups.
 //
 // Workgroup = 4 waves x 32 queries; key tiles of 32.  K and V tiles are double-buffered in LDS
-// (4 x 32 KiB at E = 256) and staged one tile ahead through ONE set of 32 registers: the next K
-// tile is loaded under the S^T product and written out before the softmax, the next V tile is
-// loaded under the softmax / O^T product -- one barrier per tile.  Q (E/2 regs), O (E/2 regs)
-// live in the 512-entry unified register file (one wave per SIMD).
+// (4 x 32 KiB at E = 256) -- one barrier per tile.  Q (E/2 regs), O (E/2 regs) live in the 512-entry unified
+// register file (one wave per SIMD): O and the S accumulators in its accumulator half, where only matrix instructions
+// reach them, Q in the vector half.  IMG = false stages one tile ahead through ONE set of 32 registers: the next K tile
+// is loaded under the S^T product and written out before the softmax, the next V tile is loaded under the softmax / O^T
+// product.
+//
+// The tile loop of the image form (one wave per SIMD: whatever the wave waits for, the matrix pipe waits for too).
+// Tile kb runs, in this order: the LDS-DMA of K(kb+2) and V(kb+1); the test of the deferred rescale on a maximum the
+// previous tile already reduced; the S^T product of tile kb+1 in ET groups of six matrix instructions, each group's K
+// fragments read from LDS while the group before it computes, with the softmax of tile kb (exp2, the fp16 split of P, the
+// lane swaps) cut into 24 steps that are handed out over those groups; the O^T product of tile kb in items of three matrix
+// instructions whose V fragments are read two items ahead, with the sum of the two S chains and the next tile's maximum
+// under its first items.  The last tile is peeled off, so that every other tile issues its successor's S^T product
+// unconditionally and that product shares a basic block with the softmax it hides.  The rescale of O is a cold branch
+// that works on the accumulator registers in place (rescale_O).  Same arithmetic in the same order as IMG = false: the
+// two forms agree bit for bit.
 //
 // Multi-head (nn.MultiheadAttention(E, H), ds_attention_h3_heads): the same kernels with a (sample, head) grid row and the head
 // width d = E / H as the template width; see MH below.
@@ -217,38 +229,74 @@ __global__ __launch_bounds__(NT) void k_attn3h(float* out, const float* __restri
   static_assert(KVEC == VVEC && KVEC % (64 * 4) == 0, "image tiles are whole LDS-DMA pieces per wave");
   const u32x4* kimg_b = IMG ? kimg + (size_t)row * nkb * KVEC : nullptr;
   const u32x4* vimg_b = IMG ? vimg + (size_t)row * nkb * VVEC : nullptr;
+  static_assert(KVEC / 256 == ET, "one LDS-DMA piece per wave, operand and group of the S^T product");
+  auto dma_piece = [&](u32x4* dst, const u32x4* src, int i) __attribute__((always_inline)) {
+    const int k = wv + 4 * i;                        // wave-uniform piece
+    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(src + 64 * k + lane),
+                                     (__attribute__((address_space(3))) void*)(dst + 64 * k), 16, 0, 0);
+  };
   auto dma = [&](u32x4* dst, const u32x4* src) __attribute__((always_inline)) {
 #pragma unroll
-    for (int i = 0; i < KVEC / 256; ++i) {
-      const int k = wv + 4 * i;                      // wave-uniform piece
-      __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(src + 64 * k + lane),
-                                       (__attribute__((address_space(3))) void*)(dst + 64 * k), 16, 0, 0);
-    }
+    for (int i = 0; i < ET; ++i) dma_piece(dst, src, i);
   };
   // ---- the two matrix products and the softmax between them, shared by both staging forms ----
-  auto qk = [&](const u32x4* Ks) __attribute__((always_inline)) {                    // S^T[key][query]
-    // two accumulation chains (even / odd 16-wide d slabs), summed at the end: consecutive matrix instructions are independent
-    f32x16 S, S1;
+  // S^T[key][query] as two accumulation chains (even / odd 16-wide d slabs) S0 + S1, which the caller sums.  The ET groups of
+  // six matrix instructions are one scheduling region each: a group's four K fragments are read from LDS while the group before
+  // it computes (one wave per SIMD: an LDS round trip that a matrix instruction waits for is idle matrix time), and under(g)
+  // is vector work of the caller's that the scheduler may spread under group g's matrix instructions.
+  auto qk = [&](const u32x4* Ks, f32x16& S0, f32x16& S1, auto&& under) __attribute__((always_inline)) {
+    f16x8 fr[2][4];                                  // [buffer][ah, al, bh, bl]
+    auto frags = [&](int s, f16x8* f) __attribute__((always_inline)) {
+      f[0] = as_f16x8(Ks[(2 * s + lh) * KB + li]);
+      f[1] = as_f16x8(Ks[NDG * KB + (2 * s + lh) * KB + li]);
+      f[2] = as_f16x8(Ks[(2 * s + 2 + lh) * KB + li]);
+      f[3] = as_f16x8(Ks[NDG * KB + (2 * s + 2 + lh) * KB + li]);
+    };
 #pragma unroll
-    for (int r = 0; r < 16; ++r) { S[r] = 0.f; S1[r] = 0.f; }
+    for (int r = 0; r < 16; ++r) { S0[r] = 0.f; S1[r] = 0.f; }
+    frags(0, fr[0]);
 #pragma unroll
     for (int s = 0; s < NS; s += 2) {
-      const f16x8 ah = as_f16x8(Ks[(2 * s + lh) * KB + li]);
-      const f16x8 al = as_f16x8(Ks[NDG * KB + (2 * s + lh) * KB + li]);
-      const f16x8 bh = as_f16x8(Ks[(2 * s + 2 + lh) * KB + li]);
-      const f16x8 bl = as_f16x8(Ks[NDG * KB + (2 * s + 2 + lh) * KB + li]);
-      S = __builtin_amdgcn_mfma_f32_32x32x16_f16(al, as_f16x8(qh[s]), S, 0, 0, 0);
+      const int g = s >> 1;
+      if (s + 2 < NS) frags(s + 2, fr[(g + 1) & 1]);
+      const f16x8 ah = fr[g & 1][0], al = fr[g & 1][1], bh = fr[g & 1][2], bl = fr[g & 1][3];
+      S0 = __builtin_amdgcn_mfma_f32_32x32x16_f16(al, as_f16x8(qh[s]), S0, 0, 0, 0);
       S1 = __builtin_amdgcn_mfma_f32_32x32x16_f16(bl, as_f16x8(qh[s + 1]), S1, 0, 0, 0);
-      S = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, as_f16x8(ql[s]), S, 0, 0, 0);
+      S0 = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, as_f16x8(ql[s]), S0, 0, 0, 0);
       S1 = __builtin_amdgcn_mfma_f32_32x32x16_f16(bh, as_f16x8(ql[s + 1]), S1, 0, 0, 0);
-      S = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, as_f16x8(qh[s]), S, 0, 0, 0);
+      S0 = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, as_f16x8(qh[s]), S0, 0, 0, 0);
       S1 = __builtin_amdgcn_mfma_f32_32x32x16_f16(bh, as_f16x8(qh[s + 1]), S1, 0, 0, 0);
+      under(g);
+      __builtin_amdgcn_sched_barrier(0);
     }
-    return S + S1;
+  };
+  // a tile's largest logit per query (= per lane; the two halves combined with one shuffle)
+  auto tile_max = [&](const f32x16& S) __attribute__((always_inline)) {
+    float mx = S[0];
+#pragma unroll
+    for (int r = 1; r < 16; ++r) mx = fmaxf(mx, S[r]);
+    return fmaxf(mx, __shfl_xor(mx, 32, 64)) * s_un;
+  };
+  // O *= alpha, in the rarely taken branch of the deferred rescale.  Written on the accumulator registers themselves: as a
+  // plain multiply the compiler copies all of O out of them at the top of EVERY tile (16 ET v_accvgpr_read per tile, and
+  // as many vector registers held through the S^T product) so that the branch finds them in place.  The matrix
+  // instructions that wrote O were issued before the barrier that ended the previous tile; the s_nop covers what is left
+  // of the last one's passes where nothing else lies between (the compiler sees no hazard inside an asm block).
+  auto rescale_O = [&](float alpha) __attribute__((always_inline)) {
+    asm volatile("s_nop 15\n\ts_nop 3" ::: "memory");
+#pragma unroll
+    for (int t = 0; t < ET; ++t)
+#pragma unroll
+      for (int r = 0; r < 16; ++r) {
+        float o = O[t][r], tmp;
+        asm volatile("v_accvgpr_read_b32 %1, %0\n\tv_mul_f32 %1, %1, %2\n\tv_accvgpr_write_b32 %0, %1" : "+a"(o), "=&v"(tmp) : "v"(alpha));
+        O[t][r] = o;
+      }
+    asm volatile("s_nop 3" ::: "memory");
   };
   if constexpr (IMG) {
-    // Software pipeline (one wave per SIMD: nothing else hides the softmax): iteration kb issues the matrix
-    // instructions of S(kb+1) and the vector instructions of softmax(S(kb)) as independent streams, then the O^T
+    // Software pipeline (one wave per SIMD: nothing else hides the softmax; the header comment has the order): tile kb
+    // issues the matrix instructions of S(kb+1) with the vector instructions of softmax(S(kb)) under them, then the O^T
     // product of tile kb.  K therefore runs one tile ahead of V: K(kb+2) -> K buffer kb&1 (last read for S(kb) in
     // iteration kb-1), V(kb+1) -> V buffer (kb+1)&1 (last read in iteration kb-1).
     dma(Kbuf, kimg_b);
@@ -256,84 +304,107 @@ __global__ __launch_bounds__(NT) void k_attn3h(float* out, const float* __restri
     if (nkb > 1) dma(Kbuf + KVEC, kimg_b + KVEC);
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
-    f32x16 S = qk(Kbuf);
-    for (int kb = 0; kb < nkb; ++kb) {
+    f32x16 S, Sn0, Sn1;
+    qk(Kbuf, Sn0, Sn1, [](int) {});
+    S = Sn0 + Sn1;
+    float mx = tile_max(S);
+    // One tile.  `last` is a literal at both call sites: every tile but the last runs the S^T product of its successor
+    // unconditionally, so that product and this tile's softmax are ONE basic block the scheduler can interleave.
+    auto tile = [&](int kb, const bool last) __attribute__((always_inline)) {
       const u32x4* Vs = Vbuf + (kb & 1) * VVEC;
-      if (kb + 2 < nkb) dma(Kbuf + (kb & 1) * KVEC, kimg_b + (size_t)(kb + 2) * KVEC);
-      if (kb + 1 < nkb) dma(Vbuf + ((kb + 1) & 1) * VVEC, vimg_b + (size_t)(kb + 1) * VVEC);
-      f32x16 Sn;
-      if (kb + 1 < nkb) Sn = qk(Kbuf + ((kb + 1) & 1) * KVEC);       // matrix pipe: independent of everything below up to the O^T product
-      // ---- online softmax of tile kb (vector pipe) ----
-      float mx = S[0];
-#pragma unroll
-      for (int r = 1; r < 16; ++r) mx = fmaxf(mx, S[r]);
-      mx = fmaxf(mx, __shfl_xor(mx, 32, 64)) * s_un;
-      if (__any(mx > m_run + thr)) {
+      // K(kb+2) and V(kb+1) travel as one LDS-DMA piece each under every group of the S^T product below: the 2 ET pieces of
+      // a wave issued back to back keep it at the address path's 64 B/clk (a quarter of the tile's matrix time at E = 256)
+      // before its first matrix instruction.  The tile before the last has no K(kb+2): it fetches the last tile's K once
+      // more, into the buffer nobody reads again, instead of a branch that would split the block.
+      u32x4* Kd = Kbuf + (kb & 1) * KVEC;
+      u32x4* Vd = Vbuf + ((kb + 1) & 1) * VVEC;
+      const u32x4* Kg = kimg_b + (size_t)min(kb + 2, nkb - 1) * KVEC;
+      const u32x4* Vg = vimg_b + (size_t)min(kb + 1, nkb - 1) * VVEC;
+      // the deferred rescale (see the other form), decided on the maximum the previous iteration left: a compare and a
+      // branch here, not a reduction.  Cold: O stays in the accumulator registers around it.
+      if (__builtin_expect(__any(mx > m_run + thr), 0)) {
         const float m_new = fmaxf(m_run, mx);
         const float alpha = expf(m_run - m_new);
         l_run = l_run * alpha;
         m_run = m_new;
-#pragma unroll
-        for (int t = 0; t < ET; ++t)
-#pragma unroll
-          for (int r = 0; r < 16; ++r) O[t][r] *= alpha;
+        rescale_O(alpha);
       }
+      // ---- online softmax of tile kb (vector pipe), in 24 steps: e^(S - m) of the 16 registers, then the fp16 split of the 8
+      // register pairs, each 16-key slab's lane swaps behind its fourth pair.  Same operations in the same order as the other form.
       float rs = 0.f;
       const float mneg = -m_run;
+      unsigned ph[2][4], pl[2][4];
+      auto softmax_step = [&](int i) __attribute__((always_inline)) {
+        if (i < 16) {
+          S[i] = __builtin_amdgcn_exp2f(__builtin_fmaf(S[i], s_un, mneg) * LOG2E);     // the difference first: see the other form
+          rs += S[i];
+        } else {
+          const int t = (i - 16) >> 2, k = (i - 16) & 3;
+          split2(S[8 * t + 2 * k], S[8 * t + 2 * k + 1], ph[t][k], pl[t][k]);
+          if (k == 3) {
 #pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        // e^(S - m): the difference FIRST (one fma with the logits' power of two: exact for nearby values), then log2(e) and the
-        // hardware exp2.  [fma(S, log2 e, -m log2 e) saves an instruction but rounds m log2 e on its own: at logits of 1e12 -- an
-        // untrained network's -- that is off by 1e5, the exponent overflows and the sample turns into NaN where the reference's
-        // softmax is a finite one-hot.]
-        S[r] = __builtin_amdgcn_exp2f(__builtin_fmaf(S[r], s_un, mneg) * LOG2E);
-        rs += S[r];
+            for (int j = 0; j < 2; ++j) {
+              u32x2 r = __builtin_amdgcn_permlane32_swap(ph[t][j], ph[t][2 + j], false, false);
+              ph[t][j] = r[0]; ph[t][2 + j] = r[1];
+              r = __builtin_amdgcn_permlane32_swap(pl[t][j], pl[t][2 + j], false, false);
+              pl[t][j] = r[0]; pl[t][2 + j] = r[1];
+            }
+          }
+        }
+      };
+      // V fragments [vh, vl] of item i = (t, slab): read two items (six matrix instructions) ahead
+      constexpr int NI = 2 * ET;
+      f16x8 vf[3][2];
+      auto vfrags = [&](int i, f16x8* f) __attribute__((always_inline)) {
+        const int t = i >> 1, sl = i & 1;
+        f[0] = as_f16x8(Vs[(2 * sl + lh) * E + 32 * t + li]);
+        f[1] = as_f16x8(Vs[4 * E + (2 * sl + lh) * E + 32 * t + li]);
+      };
+      if (!last) {
+        // matrix pipe: the S^T product of tile kb + 1, with 24 / ET softmax steps of tile kb under each of its groups
+        qk(Kbuf + ((kb + 1) & 1) * KVEC, Sn0, Sn1, [&](int g) __attribute__((always_inline)) {
+#pragma unroll
+          for (int i = 24 * g / ET; i < 24 * (g + 1) / ET; ++i) softmax_step(i);
+          dma_piece(Kd, Kg, g);
+          dma_piece(Vd, Vg, g);
+          if (g == ET - 1) { vfrags(0, vf[0]); vfrags(1, vf[1]); }
+        });
+      } else {
+#pragma unroll
+        for (int i = 0; i < 24; ++i) softmax_step(i);
+        vfrags(0, vf[0]); vfrags(1, vf[1]);
       }
       rs += __shfl_xor(rs, 32, 64);
       l_run = l_run + rs;
-      u32x4 ph[2], pl[2];
+      const u32x4 ph0{ph[0][0], ph[0][1], ph[0][2], ph[0][3]}, pl0{pl[0][0], pl[0][1], pl[0][2], pl[0][3]};
+      const u32x4 ph1{ph[1][0], ph[1][1], ph[1][2], ph[1][3]}, pl1{pl[1][0], pl[1][1], pl[1][2], pl[1][3]};
+      // ---- O^T[d][query] += V^T P^T: one scheduling region per item of three matrix instructions ----
 #pragma unroll
-      for (int t = 0; t < 2; ++t) {
-        unsigned h[4], l[4];
-#pragma unroll
-        for (int k = 0; k < 4; ++k) split2(S[8 * t + 2 * k], S[8 * t + 2 * k + 1], h[k], l[k]);
-#pragma unroll
-        for (int k = 0; k < 2; ++k) {
-          u32x2 r = __builtin_amdgcn_permlane32_swap(h[k], h[2 + k], false, false);
-          h[k] = r[0]; h[2 + k] = r[1];
-          r = __builtin_amdgcn_permlane32_swap(l[k], l[2 + k], false, false);
-          l[k] = r[0]; l[2 + k] = r[1];
+      for (int i = 0; i < NI; ++i) {
+        if (i + 2 < NI) vfrags(i + 2, vf[(i + 2) % 3]);
+        const f16x8 vh = vf[i % 3][0], vl = vf[i % 3][1];
+        const f16x8 bh = as_f16x8((i & 1) ? ph1 : ph0), bl = as_f16x8((i & 1) ? pl1 : pl0);
+        O[i >> 1] = __builtin_amdgcn_mfma_f32_32x32x16_f16(vl, bh, O[i >> 1], 0, 0, 0);
+        O[i >> 1] = __builtin_amdgcn_mfma_f32_32x32x16_f16(vh, bl, O[i >> 1], 0, 0, 0);
+        O[i >> 1] = __builtin_amdgcn_mfma_f32_32x32x16_f16(vh, bh, O[i >> 1], 0, 0, 0);
+        // the next tile's logits and their maximum: vector work under the O^T product, three matrix instructions after the
+        // S^T product's last
+        if (!last && i == 1) {
+          S = Sn0 + Sn1;
+          mx = tile_max(S);
         }
-        ph[t] = u32x4{h[0], h[1], h[2], h[3]};
-        pl[t] = u32x4{l[0], l[1], l[2], l[3]};
+        __builtin_amdgcn_sched_barrier(0);
       }
-#pragma unroll
-      for (int t = 0; t < ET; ++t) {
-#pragma unroll
-        for (int sl = 0; sl < 2; ++sl) {
-          const f16x8 vh = as_f16x8(Vs[(2 * sl + lh) * E + 32 * t + li]);
-          const f16x8 vl = as_f16x8(Vs[4 * E + (2 * sl + lh) * E + 32 * t + li]);
-          O[t] = __builtin_amdgcn_mfma_f32_32x32x16_f16(vl, as_f16x8(ph[sl]), O[t], 0, 0, 0);
-          O[t] = __builtin_amdgcn_mfma_f32_32x32x16_f16(vh, as_f16x8(pl[sl]), O[t], 0, 0, 0);
-          O[t] = __builtin_amdgcn_mfma_f32_32x32x16_f16(vh, as_f16x8(ph[sl]), O[t], 0, 0, 0);
-        }
-        if ((t & 1) == 1) __builtin_amdgcn_sched_barrier(0);
-      }
-      if (kb + 1 < nkb) S = Sn;
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
       __syncthreads();
-    }
+    };
+    for (int kb = 0; kb + 1 < nkb; ++kb) tile(kb, false);
+    tile(nkb - 1, true);
   } else {
-  if (IMG) {
-    dma(Kbuf, kimg_b);
-    dma(Vbuf, vimg_b);
-  } else {
-    k_load(0);
-    k_store(Kbuf);
-    v_load(0);
-    v_store(Vbuf);
-  }
-  if (IMG) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  k_load(0);
+  k_store(Kbuf);
+  v_load(0);
+  v_store(Vbuf);
   __syncthreads();
   for (int kb = 0; kb < nkb; ++kb) {
     const bool more = kb + 1 < nkb;
@@ -341,13 +412,7 @@ __global__ __launch_bounds__(NT) void k_attn3h(float* out, const float* __restri
     const u32x4* Vs = Vbuf + (kb & 1) * VVEC;
     u32x4* Kn = Kbuf + ((kb + 1) & 1) * KVEC;
     u32x4* Vn = Vbuf + ((kb + 1) & 1) * VVEC;
-    if (IMG) {
-      // both next-tile buffers were last read one iteration ago (before the barrier that ended it): the whole
-      // iteration covers the transfer, and the barrier at its end publishes it
-      if (more) { dma(Kn, kimg_b + (size_t)(kb + 1) * KVEC); dma(Vn, vimg_b + (size_t)(kb + 1) * VVEC); }
-    } else if (more) {
-      k_load((kb + 1) * KB);                         // flies under the S^T product
-    }
+    if (more) k_load((kb + 1) * KB);                 // flies under the S^T product
     f32x16 S;
     {
       // ---- S^T[key][query]: the same two chains, in the same order, as qk() above (the two forms agree bit for bit) ----
@@ -378,23 +443,17 @@ __global__ __launch_bounds__(NT) void k_attn3h(float* out, const float* __restri
     }
     {
       // ---- online softmax (fp32, per query = per lane; halves combined with one shuffle) ----
-      float mx = S[0];
-#pragma unroll
-      for (int r = 1; r < 16; ++r) mx = fmaxf(mx, S[r]);
-      mx = fmaxf(mx, __shfl_xor(mx, 32, 64)) * s_un;
+      const float mx = tile_max(S);
       // Deferred rescaling: O and l are kept relative to a reference maximum m_run that only moves
       // when some query's block maximum exceeds it by more than RESCALE_T (so P <= e^RESCALE_T,
       // far inside fp16's range for the hi piece).  The O-wide multiply then sits in a rarely
       // taken, wave-uniform branch instead of on every tile's critical path.
-      if (__any(mx > m_run + thr)) {
+      if (__builtin_expect(__any(mx > m_run + thr), 0)) {
         const float m_new = fmaxf(m_run, mx);
         const float alpha = expf(m_run - m_new);      // exp(-inf) = 0 on the first tile (O = 0, l = 0)
         l_run = l_run * alpha;
         m_run = m_new;
-#pragma unroll
-        for (int t = 0; t < ET; ++t)
-#pragma unroll
-          for (int r = 0; r < 16; ++r) O[t][r] *= alpha;
+        rescale_O(alpha);
       }
       float rs = 0.f;
       const float mneg = -m_run;
@@ -441,9 +500,8 @@ __global__ __launch_bounds__(NT) void k_attn3h(float* out, const float* __restri
         if ((t & 1) == 1) __builtin_amdgcn_sched_barrier(0);
       }
     }
-    if (!IMG && more) v_store(Vn);
-    if (IMG) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // this wave's LDS-DMA pieces have landed ...
-    __syncthreads();                                            // ... and so have everyone's
+    if (more) v_store(Vn);
+    __syncthreads();
   }
   }   // staging form
   float amax = 0.f;
